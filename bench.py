@@ -2,19 +2,24 @@
 """bench.py -- MTD-GAN hot-path throughput on MI355X (contract: see the task statement / DESIGN.md section 5).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload full_step|generator|inference512|patch_sampler]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up W steps, times K steps, writes the last step's outputs under --dump-outputs and prints the line
+(`value`, `ms_per_step`, ...; `roofline` and `cpu_baseline` are null).  --full adds every other leg described below.
 
 One process per GPU, backend nccl == RCCL.  `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment
 starts the N ranks itself (fresh child processes; the parent never touches the GPU); under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it is one of the ranks.  A "step" is one pass of
 the hot path over one batch of synthetic LDCT-shaped 64x64 patches (32 per GPU, weak scaling).  Prints ONE JSON line
-on rank 0.  `value` = patches/s over all ranks, inputs resident in HBM.  Extra objects:
+on rank 0.  `value` = patches/s over all ranks, inputs resident in HBM.  Extra objects (--full only):
   roofline      the dominant kernel -- the fp32-MFMA implicit-GEMM instantiation with the largest share of the step's
                 GPU time -- timed by the library's launch profiler (include/mtdgan_hip.h mtd_prof_*: two HIP events that
                 ride on the kernel's own dispatch packet, i.e. the dispatch's begin / end timestamps, the duration a
                 rocprofv3 kernel trace reports) in a second pass of the same K steps with every kernel in one stream;
   generator_fwd_bwd   BASELINE configs[1] (generator-only forward + backward, the north_star's 40 % target) timed in the
                 same process after the main workload, with its own dominant-kernel figures;
-  cpu_baseline  the CPU oracle (kind "port"), timed on rank 0 at N == 1 on a bounded sample.
+  cpu_baseline  the CPU oracle (kind "port"), timed on rank 0 at N == 1 on a bounded sample;
+  and at N > 1 the communication diagnostics (comm_diagnostics).
 """
 import argparse
 import hashlib
@@ -65,7 +70,18 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / collective plumbing only: gloo on the CPU, a trivial step (no GPU, no HIP library)")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)      # launcher test: this rank exits with 3
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline steps: roofline pass and live PMC counters, the generator and whole-slice inference "
+                         "objects, the split-bf16 Winograd and engine-API legs, the CPU baseline, the N > 1 communication diagnostics "
+                         "(the --no-* switches above still drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: set up, warm up, time --steps steps, dump the outputs, print the line -- nothing else
+        for leg in ("no_cpu_baseline", "no_roofline", "no_generator", "no_inference", "no_wino_split", "no_engine_api", "no_live_pmc"):
+            setattr(args, leg, True)
+    return args
 
 
 # ====================================================================================================== launcher
@@ -483,6 +499,71 @@ def timed(wl, steps, warmup, barrier):
     return time.perf_counter() - t0
 
 
+# ====================================================================================================== --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 15         # elements kept of a state tensor larger than this: a fixed, seeded sample (the discriminator is 274 MB)
+DUMP_SEED = 20240
+
+
+def _flat_state(module, sample):
+    """Every tensor of module.state_dict() flattened and concatenated in state_dict order, as float32; with `sample`, a tensor
+    of more than DUMP_SAMPLE elements contributes DUMP_SAMPLE of them at sorted indices drawn from a generator seeded once."""
+    import torch
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    parts = []
+    for t in module.state_dict().values():
+        f = t.detach().reshape(-1)
+        if sample and f.numel() > DUMP_SAMPLE:
+            idx = torch.randint(f.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            f = f[idx.to(f.device)]
+        parts.append(f.float())
+    return torch.cat(parts)
+
+
+def step_outputs(wl):
+    """name -> tensor: what a caller of the timed path receives from its last step."""
+    import torch
+    if wl.name == "full_step":
+        # the iteration's 16 logged values (engine.train_iteration's return value, in its order) and the trained networks
+        graphed = getattr(wl, "graphed", None)
+        if graphed is not None:
+            vals = graphed.vals
+        else:
+            _names, vals, ev, _lr = wl._logged.pending
+            if ev is not None:
+                ev.synchronize()
+        return {"logged_scalars": vals.double(),
+                "generator_state": _flat_state(wl.model.Generator, sample=False),
+                "discriminator_state_sample": _flat_state(wl.model.Discriminator, sample=True)}
+    if wl.name == "generator_fwd_bwd":
+        grads = wl.flat if wl.flat is not None else torch.cat([p.grad.reshape(-1) for p in wl.params])
+        return {"generator_grads": grads}
+    if wl.name == "inference512":
+        m = wl.last
+        return {"prediction": wl.pred, "pixel_metrics": torch.tensor([m[k] for k in ("rmse", "psnr", "ssim")], dtype=torch.float64)}
+    if wl.name == "patch_sampler":
+        lo, hi = wl.last
+        return {"patches_quarter_dose": lo, "patches_full_dose": hi}
+    raise ValueError(f"--dump-outputs: no outputs defined for workload {wl.name}")
+
+
+def dump_outputs(wl, out_dir):
+    import numpy as np
+    import torch
+    if torch.cuda.is_initialized():
+        torch.cuda.synchronize()
+    arrays = {}
+    for name, t in step_outputs(wl).items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ====================================================================================================== N > 1 diagnostics
 def comm_diagnostics(wl, dev, world, steps, barrier, ms_step, avg_max):
     """What a reader of the N > 1 line needs beside `value` ("achieved all-reduce bus GB/s vs 7 x 153 GB/s"):
@@ -580,7 +661,7 @@ def dry_run(args, rank, world):
         return float(t.item())
     dt = avg_max(time.perf_counter() - t0)
     comm = {}
-    if world > 1:
+    if world > 1 and args.full:
         # the N > 1 line's diagnostics through the same code as the GPU run (comm_diagnostics), on a stand-in workload whose
         # "model" has the partition methods it sizes the payload from and whose step all-reduces through a DataParallelSync
         from mtd_gan_amd import parallel
@@ -700,6 +781,8 @@ def main(argv=None):
     dt = avg_max(timed(wl, args.steps, args.warmup, barrier))
     ms = 1e3 * dt / args.steps
     value = per_gpu_units * ranks_seen * args.steps / dt
+    if args.dump_outputs and rank == 0:          # before any later leg runs more steps on this workload
+        dump_outputs(wl, args.dump_outputs)
 
     roofline, extra = None, {}
     pmc_tag = {"full_step": "full_step", "generator_fwd_bwd": "generator", "inference512": "inference512"}.get(wl.name)
@@ -787,7 +870,7 @@ def main(argv=None):
     # ---- the N > 1 line's diagnostics (also under MTD_FORCE_DP=1 on one rank): after everything that feeds the line, since the
     # last of them runs the step with its collectives stubbed
     comm = {}
-    if wl.name == "full_step" and dist.is_initialized():
+    if args.full and wl.name == "full_step" and dist.is_initialized():
         comm = comm_diagnostics(wl, dev, world, args.steps, barrier, ms, avg_max)
 
     if rank == 0 and wl.name == "full_step":

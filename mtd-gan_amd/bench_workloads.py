@@ -122,7 +122,7 @@ class InferenceWorkload:
         x, y = synthetic_ldct(self.slices, seed=1234 + rank, size=512)
         self.x, self.y = x.to(dev), y.to(dev)
         self.world = world
-        self.last = None
+        self.last = self.pred = None
 
     def step(self):
         from . import kernels as K
@@ -130,6 +130,7 @@ class InferenceWorkload:
         with torch.no_grad():
             pred = self.G(self.x)
             self.last = M.pixel_metrics(self.x, self.y, K.clip01(pred))
+        self.pred = pred                # (bench.py --dump-outputs)
 
     def config(self, world):
         return {"workload": "Whole-slice generator inference + pixel metrics (BASELINE configs[4])", "per_gpu_batch": self.slices,

@@ -298,7 +298,7 @@ def test_live_pmc_lookup_and_refusals(monkeypatch):
     monkeypatch.setattr(shutil, "which", lambda _n: None)
     monkeypatch.setattr(os.path, "exists", lambda p_, _e=os.path.exists: False if p_ == "/opt/rocm/bin/rocprofv3" else _e(p_))
     assert bench.live_pmc_collect("full_step") is None and not started
-    assert bench.parse(["--no-live-pmc"]).no_live_pmc and not bench.parse([]).no_live_pmc
+    assert bench.parse(["--full", "--no-live-pmc"]).no_live_pmc and not bench.parse(["--full"]).no_live_pmc
 
 
 def test_lockstep_driver_groups_aligned_launches(monkeypatch):

@@ -7,5 +7,5 @@ timeout -k 10 700 python tests/dp_two_ranks_one_gpu.py > $O/dp2.log 2>&1; rc=$?
 grep -v "amdgpu.ids" $O/dp2.log | tail -20
 echo "exit code $rc"
 [ $rc -eq 0 ] || exit $rc
-MTD_DP_SHARE_GPU=1 timeout -k 10 400 python bench.py --gpus 2 --steps 5 --warmup 2 --no-roofline --no-cpu-baseline --no-generator --no-inference --no-engine-api > $O/dp2_bench.json 2> $O/dp2_bench.err; rc=$?
+MTD_DP_SHARE_GPU=1 timeout -k 10 400 python bench.py --gpus 2 --steps 5 --warmup 2 --full --no-roofline --no-cpu-baseline --no-generator --no-inference --no-engine-api > $O/dp2_bench.json 2> $O/dp2_bench.err; rc=$?
 cut -c1-600 $O/dp2_bench.json; echo "bench exit code $rc"

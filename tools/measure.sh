@@ -46,5 +46,5 @@ PY
   # utilisation only from passes whose source hash matches)
   bash tools/install_profiles.sh $R nogit || exit 1
 fi
-timeout -k 10 400 python bench.py > $O/bench_full.json 2> $O/bench_full.err || { echo "bench failed"; tail -20 $O/bench_full.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err || { echo "bench failed"; tail -20 $O/bench_full.err; exit 1; }
 cut -c1-400 $O/bench_full.json; echo

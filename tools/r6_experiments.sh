@@ -40,7 +40,7 @@ exp4() {
 timeout -k 10 400 python -m pytest tests/test_discriminator_gpu.py -x -q -k "power or spectral" > $O/exp4_tests.log 2>&1 || { tail -40 $O/exp4_tests.log; exit 1; }
 tail -2 $O/exp4_tests.log
 bash tools/ab_step.sh "MTD_SN_FUSED_ITERS=0" "MTD_SN_FUSED_ITERS=1" 2 | tee $O/exp4_ab.txt
-MTD_FORCE_DP=1 timeout -k 10 300 python bench.py --steps 30 --warmup 8 $NOX > $O/fdp.json 2> $O/fdp.err || { tail -20 $O/fdp.err; exit 1; }
+MTD_FORCE_DP=1 timeout -k 10 300 python bench.py --steps 30 --warmup 8 --full $NOX > $O/fdp.json 2> $O/fdp.err || { tail -20 $O/fdp.err; exit 1; }
 python - <<'PY'
 import json
 z = json.loads(open("gpurun_out/fdp.json").read().strip().splitlines()[-1])
@@ -163,7 +163,7 @@ exp16() {
 timeout -k 10 800 python -m pytest tests -m gpu -x -q > $O/gpu_tests_final.log 2>&1; echo "gpu suite exit $?"; tail -3 $O/gpu_tests_final.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -2
 for cfg in "MTD_FORCE_DP=0" "MTD_FORCE_DP=1" "MTD_FORCE_DP=0" "MTD_FORCE_DP=1"; do
-  env $cfg timeout -k 10 300 python bench.py --steps 30 --warmup 8 $NOX 2>/dev/null > $O/fdp_$cfg.json
+  env $cfg timeout -k 10 300 python bench.py --steps 30 --warmup 8 --full $NOX 2>/dev/null > $O/fdp_$cfg.json
   python -c "
 import sys,json; z=json.loads(open('$O/fdp_$cfg.json').read().strip().splitlines()[-1]); print('[$cfg]', z['ms_per_step'], z.get('ms_per_step_collectives_stubbed'), z.get('comm_exposed_ms'), z.get('graph_error'))"
 done | tee $O/exp16_fdp.txt
@@ -274,7 +274,7 @@ find $O/prof_conc -name "*.db" -size +30M -delete
 # round 6, end of round: the forced data-parallel line beside the plain one and the two-rank rehearsal at the final tree
 exp26() {
 for cfg in "MTD_FORCE_DP=0" "MTD_FORCE_DP=1" "MTD_FORCE_DP=0" "MTD_FORCE_DP=1"; do
-  env $cfg timeout -k 10 300 python bench.py --steps 30 --warmup 8 $NOX 2>/dev/null > $O/fdp_$cfg.json
+  env $cfg timeout -k 10 300 python bench.py --steps 30 --warmup 8 --full $NOX 2>/dev/null > $O/fdp_$cfg.json
   python -c "
 import sys,json; z=json.loads(open('$O/fdp_$cfg.json').read().strip().splitlines()[-1]); print('[$cfg]', z['ms_per_step'], z.get('ms_per_step_collectives_stubbed'), z.get('comm_exposed_ms'), z.get('graph_error'))"
 done | tee $O/exp26_fdp.txt
