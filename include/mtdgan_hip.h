@@ -298,6 +298,23 @@ int mtd_spec_mix_any(const float* R, const float* w2t, const float* b2, float* T
 int mtd_irfft_rows_any(const float* T, float* out, int out_ld, const float* add1, int add1_ld, const float* add2,
                        int add2_ld, int B, int S, void* stream);
 
+/* The same three steps for maps of any size 16 <= H, W <= 512, chosen independently (odd, non-square and prime sides included;
+ * the shapes the entry points above refuse).  Spectra as above, [B][kw 0..W/2][h 0..H-1][Re 32 | Im 32] with W/2 + 1 columns
+ * (odd W: the last column is an ordinary one, weight 2 on the way back), ortho 1/sqrt(H W) overall.  Transforms: mixed radix
+ * 2/3/4/5/7 for 7-smooth lengths, Bluestein (power-of-two convolution of length M >= 2N - 1) otherwise.  ws: a device buffer of
+ * at least mtd_spectral_gen_ws_bytes(B, H, W) bytes (the Bluestein filter spectra; 0 = arguments out of range), used in
+ * stream order.  mtd_spec_mix_gen zeroes the imaginary halves of column 0 and (even W) column W/2 of T.  R and T: 4-byte
+ * aligned; no other alignment needed.  Arguments out of range or null pointers: MTD_EINVAL, nothing launched.
+ * mtd_spectral_gen_plan(n, out) reports the plan of a length: returns the number of passes, out[0] = Bluestein length M
+ * (0: mixed radix), out[1..] = the radices in decimation-in-frequency order (out: 16 ints). */
+size_t mtd_spectral_gen_ws_bytes(int B, int H, int W);
+int mtd_spectral_gen_plan(int n, int* out);
+int mtd_rfft_rows_gen(const float* x, int x_ld, float* R, int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+int mtd_spec_mix_gen(const float* R, const float* w2t, const float* b2, float* T, int B, int H, int W, void* ws, size_t ws_bytes,
+                     void* stream);
+int mtd_irfft_rows_gen(const float* T, float* out, int out_ld, const float* add1, int add1_ld, const float* add2, int add2_ld,
+                       int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+
 /* 64x64 transpose of the 1x1 spectral conv weight (W2[o][k] -> W2T[k][o]). */
 int mtd_transpose64(const float* src, float* dst, void* stream);
 /* n transposes in one launch; ptrs_dev (device): [src_0, dst_0, src_1, dst_1, ...] (the 21 blocks' mix weights, once per step) */

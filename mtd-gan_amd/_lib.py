@@ -220,6 +220,11 @@ def lib():
     sig("mtd_rfft_rows_any", ci, vp, ci, vp, ci, ci, vp)
     sig("mtd_spec_mix_any", ci, vp, vp, vp, vp, ci, ci, vp)
     sig("mtd_irfft_rows_any", ci, vp, vp, ci, vp, ci, vp, ci, ci, ci, vp)
+    sig("mtd_spectral_gen_ws_bytes", sz, ci, ci, ci)
+    sig("mtd_spectral_gen_plan", ci, ci, vp)
+    sig("mtd_rfft_rows_gen", ci, vp, ci, vp, ci, ci, ci, vp, sz, vp)
+    sig("mtd_spec_mix_gen", ci, vp, vp, vp, vp, ci, ci, ci, vp, sz, vp)
+    sig("mtd_irfft_rows_gen", ci, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, vp, sz, vp)
     sig("mtd_act_grad", ci, vp, ci, vp, ci, vp, ci, ll, ci, cf, vp)
     sig("mtd_copy_channels", ci, vp, ci, vp, ci, ll, ci, ci, vp)
     sig("mtd_upsample2x_fwd", ci, vp, ci, vp, ci, ci, ci, ci, ci, vp)
@@ -301,6 +306,7 @@ EXPORTS = [
     "mtd_pcgrad_gram", "mtd_pcgrad_combine", "mtd_adamw_multi", "mtd_adamw_multi_dyn", "mtd_adamw_multi_pre", "mtd_loss_terms_ws_bytes", "mtd_loss_terms",
     "mtd_loss_term_grads", "mtd_clip01", "mtd_clip01_bwd", "mtd_edge_loss_ws_bytes", "mtd_edge_loss",
     "mtd_prof_enable", "mtd_prof_collect", "mtd_conv_igemm_override", "mtd_conv_wgrad_override", "mtd_upload", "mtd_image_metrics_ws_bytes", "mtd_image_metrics", "mtd_rfft_rows_any", "mtd_spec_mix_any", "mtd_irfft_rows_any",
+    "mtd_spectral_gen_ws_bytes", "mtd_spectral_gen_plan", "mtd_rfft_rows_gen", "mtd_spec_mix_gen", "mtd_irfft_rows_gen",
     "mtd_conv_wgrad_slabs", "mtd_conv_wgrad_slabs_rfft", "mtd_conv_wgrad_reduce_blocks", "mtd_conv_wgrad_reduce_multi", "mtd_spec_mix_wgrad_reduce_multi",
     "mtd_foreground_bbox", "mtd_window_patches", "mtd_hu_window", "mtd_add", "mtd_transpose64_multi", "mtd_upsample2x_bwd_masked",
     "mtd_prof_mode", "mtd_pcgrad_coeff", "mtd_pcgrad_axpy", "mtd_conv_igemm_multi_ws_bytes", "mtd_conv_igemm_multi",

@@ -47,8 +47,25 @@ class _BlockFn(torch.autograd.Function):
         return gx, grads["dw_img"], grads["db_img"], grads["dw_fft"], grads["db_fft"]
 
 
+def _any_size_ok(x, C, who, params):
+    """The opt-in path of allow_any_size: inference (no gradient required) on (B, C, H, W) with 16 <= H, W <= 512."""
+    if x.dim() != 4 or x.shape[1] != C:
+        return False
+    H, W = x.shape[2], x.shape[3]
+    if not (GP.GEN_MIN <= H <= GP.GEN_MAX and GP.GEN_MIN <= W <= GP.GEN_MAX):
+        raise NotImplementedError(f"{who} HIP path: map sides {GP.GEN_MIN} .. {GP.GEN_MAX} (allow_any_size), got {tuple(x.shape)}")
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        return False          # (the caller's usual checks then raise: training is implemented for 64 x 64 patches)
+    return True
+
+
 class FFT_ConvBlock(nn.Module):
-    """x + relu(conv3x3(x)) + irfft2(relu(conv1x1([Re;Im] rfft2(x))))  -- reference networks.py:15-36."""
+    """x + relu(conv3x3(x)) + irfft2(relu(conv1x1([Re;Im] rfft2(x))))  -- reference networks.py:15-36.
+
+    allow_any_size (class attribute, off by default): when True and no gradient is required, any (B, 32, H, W) with
+    16 <= H, W <= 512 runs (inference on the general-length spectral path, csrc/resfft_gen.hip)."""
+
+    allow_any_size = False
 
     def __init__(self, out_channels):
         super().__init__()
@@ -57,6 +74,10 @@ class FFT_ConvBlock(nn.Module):
 
     def forward(self, x):
         _require_cuda(x, "FFT_ConvBlock")
+        if self.allow_any_size and _any_size_ok(x, 32, "FFT_ConvBlock", self.parameters()) and tuple(x.shape[2:]) != (64, 64):
+            xn = x.permute(0, 2, 3, 1).contiguous().float()
+            out, _ = GP.block_forward(xn, self.img_conv.weight, self.img_conv.bias, self.fft_conv.weight, self.fft_conv.bias, False)
+            return out.permute(0, 3, 1, 2)
         if x.shape[1] != 32 or x.shape[2] != 64 or x.shape[3] != 64:
             raise NotImplementedError("FFT_ConvBlock HIP path: 32 channels, 64x64 patches (training hot path)")
         xn = x.permute(0, 2, 3, 1).contiguous()                 # layout plumbing only
@@ -119,7 +140,12 @@ def _unflatten_gen(flat, nlayers, as_grad=False):
 
 class ResFFT_Generator(nn.Module):
     """Reference networks.py:38-164.  RED-CNN-style 11 conv + 11 conv-transpose (stride 1) with additive
-    skips and 21 Res-FFT-Conv blocks.  HIP path covers the MTD-GAN configuration (1, 32, 10, 3, 1)."""
+    skips and 21 Res-FFT-Conv blocks.  HIP path covers the MTD-GAN configuration (1, 32, 10, 3, 1).
+
+    allow_any_size (class attribute, off by default): when True and no gradient is required, any (B, 1, H, W) with
+    16 <= H, W <= 512 runs; by default inference takes the squares 64 / 128 / 256 / 512 and training 64 x 64 patches."""
+
+    allow_any_size = False
 
     def __init__(self, in_channels=1, out_channels=96, num_layers=10, kernel_size=5, padding=0):
         super().__init__()
@@ -167,7 +193,8 @@ class ResFFT_Generator(nn.Module):
         _require_cuda(x, "ResFFT_Generator")
         if self._cfg != (1, 32, 10, 3, 1):
             raise NotImplementedError("ResFFT_Generator HIP path is built for MTD_GAN_Method's (1,32,10,3,1) configuration")
-        if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != x.shape[3] or x.shape[2] not in (64, 128, 256, 512):
+        any_size = self.allow_any_size and _any_size_ok(x, 1, "ResFFT_Generator", self.parameters())
+        if not any_size and (x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != x.shape[3] or x.shape[2] not in (64, 128, 256, 512)):
             raise NotImplementedError(f"ResFFT_Generator HIP path expects (B,1,S,S) with S in 64/128/256/512, got {tuple(x.shape)}")
         if x.shape[2] != 64 and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("ResFFT_Generator HIP path: maps larger than 64 x 64 are inference-only (use torch.no_grad())")

@@ -11,28 +11,35 @@ from . import kernels as K
 from .kernels import ACT_NONE, ACT_RELU
 
 CH = 32
+GEN_MIN, GEN_MAX = 16, 512     # sides the general-length spectral path takes (csrc/resfft_gen.hip), inference only
 
 
 # ------------------------------------------------------------------------------------------------ block
 def block_forward(x, w_img, b_img, w_fft, b_fft, save, w2t=None):
-    """x: (B,64,64,32).  Returns (out, saved) with saved = (x, img, S, Z) when save."""
+    """x: (B,64,64,32), or without save any (B,H,W,32) with 16 <= H, W <= 512.  Returns (out, saved) with saved = (x, img, S, Z)
+    when save."""
     B, H, W, _ = x.shape
     g = K.geom_fwd(B, H, W, 3, 1, 1)
     img = K.empty_nhwc(B, H, W, CH, x)
     if H != 64 or W != 64:
-        # whole-slice inference (reference engine.py:89,129): LDS-resident transforms of side 128 / 256 / 512, forward only
+        # whole-slice inference (reference engine.py:89,129), forward only: LDS-resident transforms of side 128 / 256 / 512
+        # for the power-of-two squares, the general-length transforms (mixed radix / Bluestein) for any other 16 .. 512 per side
         if save:
             raise RuntimeError("FFT_ConvBlock: training is implemented for 64 x 64 patches; larger maps are inference-only")
-        if H != W or H not in (128, 256, 512):
-            raise RuntimeError(f"FFT_ConvBlock: unsupported map size {H} x {W} (64, 128, 256 or 512 square)")
+        if H == W and H in (128, 256, 512):
+            spectral = K.spectral_branch_any
+        elif GEN_MIN <= H <= GEN_MAX and GEN_MIN <= W <= GEN_MAX:
+            spectral = K.spectral_branch_gen
+        else:
+            raise RuntimeError(f"FFT_ConvBlock: unsupported map size {H} x {W} ({GEN_MIN} .. {GEN_MAX} per side)")
         out = K.empty_nhwc(B, H, W, CH, x)
         if K.conv_relu_add_ok(x, w_img, g, CH, CH, CH * 9, 9, img, bias=b_img, add1=x):
             # img = x + relu(conv3x3(x) + b) in one launch (MTD_ACT_RELU_ADD): the closing row transform then adds ONE operand
             K.conv(x, w_img, g, CH, CH, CH * 9, 9, img, bias=b_img, add1=x, act=K.ACT_RELU_ADD)
-            K.spectral_branch_any(x, w2t if w2t is not None else K.transpose64(w_fft), b_fft, out, add1=img)
+            spectral(x, w2t if w2t is not None else K.transpose64(w_fft), b_fft, out, add1=img)
         else:
             K.conv(x, w_img, g, CH, CH, CH * 9, 9, img, bias=b_img, act=ACT_RELU)
-            K.spectral_branch_any(x, w2t if w2t is not None else K.transpose64(w_fft), b_fft, out, add1=x, add2=img)
+            spectral(x, w2t if w2t is not None else K.transpose64(w_fft), b_fft, out, add1=x, add2=img)
         return out, None
     if w2t is None:
         w2t = K.transpose64(w_fft)

@@ -1123,6 +1123,30 @@ def spectral_branch_any(x, w2t, b2, out, add1=None, add2=None):
     return out
 
 
+
+def spectral_branch_gen(x, w2t, b2, out, add1=None, add2=None):
+    """The same for an NHWC map of any size 16 <= H, W <= 512 (csrc/resfft_gen.hip: mixed radix or Bluestein per side; the
+    power-of-two squares have spectral_branch_any).  Forward only."""
+    L = _lib.lib()
+    B, H, W = x.shape[0], x.shape[1], x.shape[2]
+    for t in (x, out, add1, add2):      # (the kernels address pixel (b, h, w) as ((b H + h) W + w) * ld)
+        if t is not None and (tuple(t.shape[:3]) != (B, H, W) or t.stride(1) != W * ld_of(t) or t.stride(0) != H * W * ld_of(t)):
+            raise ValueError(f"spectral_branch_gen: NHWC maps with packed pixels expected, got {tuple(t.shape)} {t.stride()}")
+    need = L.mtd_spectral_gen_ws_bytes(B, H, W)
+    if need == 0:
+        raise ValueError(f"spectral_branch_gen: map {H} x {W} (batch {B}) outside 16 .. 512 per side")
+    ws = workspace(need, x.device)
+    R = torch.empty((B, W // 2 + 1, H, 64), dtype=torch.float32, device=x.device)
+    T = torch.empty_like(R)
+    s = stream_ptr()
+    check(L.mtd_rfft_rows_gen(x.data_ptr(), ld_of(x), R.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), s), "mtd_rfft_rows_gen")
+    check(L.mtd_spec_mix_gen(R.data_ptr(), w2t.data_ptr(), b2.data_ptr(), T.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(), s),
+          "mtd_spec_mix_gen")
+    check(L.mtd_irfft_rows_gen(T.data_ptr(), out.data_ptr(), ld_of(out), _ptr(add1), ld_of(add1) if add1 is not None else 0,
+                               _ptr(add2), ld_of(add2) if add2 is not None else 0, B, H, W, ws.data_ptr(), ws.numel(), s),
+          "mtd_irfft_rows_gen")
+    return out
+
 def transpose64_all(weights):
     """Transposes of many 64 x 64 matrices in ONE launch (the mix weights of all Res-FFT blocks of a forward pass), cached
     until the weights change (dropped by weights_changed() like the packed conv weights).  Returns {id(w): transposed}."""

@@ -1,0 +1,131 @@
+"""Generator inference on slices of any size 16 .. 512 per side (allow_any_size: the general-length spectral path of
+csrc/resfft_gen.hip -- mixed radix for 7-smooth sides, Bluestein otherwise) against the CPU oracle's torch.fft path."""
+import os
+import sys
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import mtdgan_oracle as orc  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+from _metrics import rel  # noqa: E402
+
+
+@pytest.fixture
+def any_size(monkeypatch):
+    from mtd_gan_amd.arch.Ours.networks import FFT_ConvBlock, ResFFT_Generator
+    monkeypatch.setattr(ResFFT_Generator, "allow_any_size", True)
+    monkeypatch.setattr(FFT_ConvBlock, "allow_any_size", True)
+
+
+def _generator():
+    from mtd_gan_amd.arch.Ours.networks import ResFFT_Generator
+    g = orc.seeded_fill(orc.g_param_shapes(), seed=7)
+    G = ResFFT_Generator(1, 32, 10, 3, 1)
+    G.load_state_dict(g)
+    return G.cuda().eval(), g
+
+
+def _slices(B, H, W, seed):
+    """Synthetic low-dose / full-dose pairs cropped to H x W (the phantom generator makes squares)."""
+    x, y = orc.synthetic_ldct(B, seed=seed, size=max(H, W))
+    return x[:, :, :H, :W].contiguous(), y[:, :, :H, :W].contiguous()
+
+
+def _block(i=3):
+    from mtd_gan_amd.arch.Ours.networks import FFT_ConvBlock
+    g = orc.seeded_fill(orc.g_param_shapes(), seed=11)
+    p = f"enforce.{i}."
+    blk = FFT_ConvBlock(32)
+    blk.load_state_dict({k[len(p):]: v for k, v in g.items() if k.startswith(p)})
+    return blk.cuda(), [g[p + n] for n in ("img_conv.weight", "img_conv.bias", "fft_conv.weight", "fft_conv.bias")]
+
+
+@pytest.mark.parametrize("shape", [(2, 32, 96, 96), (1, 32, 100, 77), (3, 32, 45, 64), (1, 32, 384, 512), (1, 32, 512, 300),
+                                   (1, 32, 509, 509)])
+def test_block_matches_oracle(hip_lib, any_size, shape):
+    blk, w = _block()
+    x = torch.relu(torch.randn(shape, generator=torch.Generator().manual_seed(sum(shape))))
+    with torch.no_grad():
+        out = blk(x.cuda())
+    assert tuple(out.shape) == shape
+    assert rel(out.cpu(), orc.resfft_block(x, *w)) < 1e-3
+
+
+@pytest.mark.parametrize("shape", [(2, 1, 96, 96), (2, 1, 100, 77), (1, 1, 384, 512), (1, 1, 509, 509)])
+def test_generator_matches_oracle(hip_lib, any_size, shape):
+    G, g = _generator()
+    B, _, H, W = shape
+    x, y = _slices(B, H, W, seed=H + W)
+    with torch.no_grad():
+        out = G(x.cuda())
+    assert tuple(out.shape) == shape
+    ref = orc.generator_forward(g, x)
+    assert rel(out.cpu(), ref) < 1e-3
+    assert abs(orc.psnr(out.cpu().clip(0, 1), y).item() - orc.psnr(ref.clip(0, 1), y).item()) < 0.01
+
+
+@pytest.mark.parametrize("H,W", [(77, 100), (45, 75)])
+def test_batch_equals_single_slices(hip_lib, any_size, H, W):
+    """77 = 7 x 11 (Bluestein along H), 45 x 75 (odd 7-smooth sides): slices are independent, bit for bit."""
+    G, _ = _generator()
+    x, _ = _slices(3, H, W, seed=5)
+    xd = x.cuda()
+    with torch.no_grad():
+        out = G(xd)
+        singles = [G(xd[i:i + 1]) for i in range(3)]
+    for i in range(3):
+        assert torch.equal(out[i:i + 1], singles[i]), i
+
+
+def test_existing_sizes_unchanged(hip_lib, monkeypatch):
+    from mtd_gan_amd.arch.Ours.networks import FFT_ConvBlock, ResFFT_Generator
+    G, _ = _generator()
+    blk, _ = _block()
+    runs = {}
+    for flag in (False, True):
+        monkeypatch.setattr(ResFFT_Generator, "allow_any_size", flag)
+        monkeypatch.setattr(FFT_ConvBlock, "allow_any_size", flag)
+        with torch.no_grad():
+            for S in (64, 128, 512):
+                x, _ = orc.synthetic_ldct(1, seed=S, size=S)
+                runs[(flag, S)] = G(x.cuda())
+            xb = torch.relu(torch.randn(2, 32, 64, 64, generator=torch.Generator().manual_seed(1)))
+            runs[(flag, "blk")] = blk(xb.cuda())
+    for k in (64, 128, 512, "blk"):
+        assert torch.equal(runs[(False, k)], runs[(True, k)]), k
+
+
+def test_refusals(hip_lib, any_size):
+    G, _ = _generator()
+    blk, _ = _block()
+    with torch.no_grad():
+        for shape in ((1, 15, 64), (1, 513, 512)):
+            with pytest.raises(NotImplementedError):
+                G(torch.zeros((1,) + shape, device="cuda"))
+            with pytest.raises(NotImplementedError):
+                blk(torch.zeros((1, 32) + shape[1:], device="cuda"))
+    with pytest.raises(NotImplementedError):
+        G(torch.zeros(1, 1, 96, 96, device="cuda"))            # grad mode on, parameters require grad
+    with pytest.raises(NotImplementedError):
+        blk(torch.zeros(1, 32, 96, 96, device="cuda"))
+
+
+def test_eval_loops_on_an_odd_slice(hip_lib, any_size, tmp_path):
+    from mtd_gan_amd import engine
+    from mtd_gan_amd.arch.Ours.networks import MTD_GAN_Method
+    torch.manual_seed(3)
+    m = MTD_GAN_Method().cuda()
+    g = orc.seeded_fill(orc.g_param_shapes(), seed=7)
+    m.Generator.load_state_dict(g)
+    x, y = _slices(1, 100, 77, seed=9)
+    loader = [dict(n_20=x, n_100=y, path_n_20=["L000_0001.dcm"], path_n_100=["L000_0001.dcm"])]
+    v = engine.valid_MTD_GAN_Ours(m, torch.nn.L1Loss(), loader, torch.device("cuda"), 0, None, 1)
+    ref = orc.generator_forward(g, x)
+    assert abs(v["L1_loss"] - (ref - y).abs().mean().item()) < 1e-5
+    t = engine.test_MTD_GAN_Ours(m, torch.nn.L1Loss(), loader, torch.device("cuda"), str(tmp_path))
+    assert abs(t["pred_psnr"] - orc.psnr(ref.clip(0, 1), y).item()) < 0.01
+    assert abs(t["pred_ssim"] - orc.ssim(ref.clip(0, 1), y).item()) < 2e-5
