@@ -135,6 +135,22 @@ int mtd_conv_winograd(const mtd_conv_args* a, void* stream);
 int mtd_conv_winograd_group_ok(const mtd_conv_args* a, int count);
 int mtd_conv_winograd_group(const mtd_conv_args* a, int count, void* stream);
 
+/* ---- Binary16 activation storage for whole-slice inference (engine.py:89,129: the generator on whole 512 x 512 slices).
+ * Arithmetic, weights and biases stay fp32; only the maps that one launch stores for a later one are IEEE binary16, rounded to
+ * nearest-even from the fp32 value and saturated at +-65504.  mtd_conv_st_args = mtd_conv_args plus the storage type of a.in, a.add1
+ * and a.out: a pointer of a binary16 operand travels behind its float type, its stride counts ELEMENTS as before.
+ *   mtd_conv_winograd_st   the generator's 32 -> 32 channel layers (networks.py:99-160 encoder / decoder, :18,32 the block's conv) on
+ *                          the persistent F(2x4, 3x3) kernel, in / add1 / out all MTD_ST_F16 (all MTD_ST_F32: mtd_conv_winograd
+ *                          itself).  a.w = the fp32 transformed weights of mtd_winograd_weights; one residual operand at most,
+ *                          MTD_ACT_RELU_ADD included, no scale / mask / out2 / add2.  Anything else: MTD_EINVAL, nothing is launched.
+ *   mtd_conv_direct_st     the first layer (networks.py:97 encoder.0, 1 -> N: in MTD_ST_F32, out MTD_ST_F16, no add / mask operands,
+ *                          3x3 "same" geometry) and the last (networks.py:162 decoder.0, C -> 1: in MTD_ST_F16, add1 and out
+ *                          MTD_ST_F32).  Anything else: MTD_EINVAL. */
+enum { MTD_ST_F32 = 0, MTD_ST_F16 = 1 };
+typedef struct { mtd_conv_args a; int in_type, add1_type, out_type; } mtd_conv_st_args;
+int mtd_conv_winograd_st(const mtd_conv_st_args* a, void* stream);
+int mtd_conv_direct_st(const mtd_conv_st_args* a, void* stream);
+
 /* ---- Winograd F(3x3, 2x2) for the 4x4 / stride-2 / padding-1 layers (csrc/conv_wino_s2.h; arch/Ours/networks.py:185-215 down1..3:
  * Conv2d(k4, s2, p1) forward and its four-parity data gradient): the forward conv is a 2x2 stride-1 conv over the 4 C channels of
  * the space-to-depth image of the padded input (never formed: each phase is read at pixel stride 2), each parity class of the
@@ -297,6 +313,13 @@ int mtd_rfft_rows_any(const float* x, int x_ld, float* R, int B, int S, void* st
 int mtd_spec_mix_any(const float* R, const float* w2t, const float* b2, float* T, int B, int S, void* stream);
 int mtd_irfft_rows_any(const float* T, float* out, int out_ld, const float* add1, int add1_ld, const float* add2,
                        int add2_ld, int B, int S, void* stream);
+/* The same three launches with binary16 storage (networks.py:21-36 on whole slices, S = 128 / 256 / 512): x, R, T, add1, add2 and out
+ * are binary16 maps with the layouts above (strides in elements and multiples of 4, 16-byte aligned bases); w2t and b2 stay
+ * fp32, and so does every value inside a launch (the LDS lines, the transforms, the MFMA channel mix). */
+int mtd_rfft_rows_any_h(const void* x, int x_ld, void* R, int B, int S, void* stream);
+int mtd_spec_mix_any_h(const void* R, const float* w2t, const float* b2, void* T, int B, int S, void* stream);
+int mtd_irfft_rows_any_h(const void* T, void* out, int out_ld, const void* add1, int add1_ld, const void* add2,
+                         int add2_ld, int B, int S, void* stream);
 
 /* The same three steps for maps of any size 16 <= H, W <= 512, chosen independently (odd, non-square and prime sides included;
  * the shapes the entry points above refuse).  Spectra as above, [B][kw 0..W/2][h 0..H-1][Re 32 | Im 32] with W/2 + 1 columns

@@ -47,6 +47,14 @@ class ConvArgs(C.Structure):
                 ("tile_ctr", C.c_void_p), ("tile_ctr_len", C.c_int)]
 
 
+ST_F32, ST_F16 = 0, 1      # MTD_ST_*: storage type of an activation map
+
+
+class ConvStArgs(C.Structure):
+    """mtd_conv_st_args: a conv launch plus the storage types of its input, residual operand and output."""
+    _fields_ = [("a", ConvArgs), ("in_type", C.c_int), ("add1_type", C.c_int), ("out_type", C.c_int)]
+
+
 class WgradArgs(C.Structure):
     _fields_ = [("g", Geom),
                 ("p", C.c_void_p), ("p_ld", C.c_int), ("N", C.c_int),
@@ -220,6 +228,11 @@ def lib():
     sig("mtd_rfft_rows_any", ci, vp, ci, vp, ci, ci, vp)
     sig("mtd_spec_mix_any", ci, vp, vp, vp, vp, ci, ci, vp)
     sig("mtd_irfft_rows_any", ci, vp, vp, ci, vp, ci, vp, ci, ci, ci, vp)
+    sig("mtd_rfft_rows_any_h", ci, vp, ci, vp, ci, ci, vp)
+    sig("mtd_spec_mix_any_h", ci, vp, vp, vp, vp, ci, ci, vp)
+    sig("mtd_irfft_rows_any_h", ci, vp, vp, ci, vp, ci, vp, ci, ci, ci, vp)
+    sig("mtd_conv_winograd_st", ci, C.POINTER(ConvStArgs), vp)
+    sig("mtd_conv_direct_st", ci, C.POINTER(ConvStArgs), vp)
     sig("mtd_spectral_gen_ws_bytes", sz, ci, ci, ci)
     sig("mtd_spectral_gen_plan", ci, ci, vp)
     sig("mtd_rfft_rows_gen", ci, vp, ci, vp, ci, ci, ci, vp, sz, vp)
@@ -317,6 +330,7 @@ EXPORTS = [
     "mtd_conv_wgrad_plan_cfg", "mtd_conv_winograd_patch_w", "mtd_conv_winograd_f4_min_w", "mtd_conv_relu_add_ok", "mtd_dropout_mask", "mtd_scale_by", "mtd_scalar_sums", "mtd_zero_multi", "mtd_checksum_multi",
     "mtd_set_option", "mtd_get_option", "mtd_lab_build",
     "mtd_winograd_s2_kmap", "mtd_winograd_s2_weights", "mtd_conv_winograd_s2_ok", "mtd_conv_winograd_s2_ws_bytes", "mtd_conv_winograd_s2",
+    "mtd_conv_winograd_st", "mtd_conv_direct_st", "mtd_rfft_rows_any_h", "mtd_spec_mix_any_h", "mtd_irfft_rows_any_h",
 ]
 
 

@@ -143,9 +143,15 @@ class ResFFT_Generator(nn.Module):
     skips and 21 Res-FFT-Conv blocks.  HIP path covers the MTD-GAN configuration (1, 32, 10, 3, 1).
 
     allow_any_size (class attribute, off by default): when True and no gradient is required, any (B, 1, H, W) with
-    16 <= H, W <= 512 runs; by default inference takes the squares 64 / 128 / 256 / 512 and training 64 x 64 patches."""
+    16 <= H, W <= 512 runs; by default inference takes the squares 64 / 128 / 256 / 512 and training 64 x 64 patches.
+
+    activation_dtype (class attribute, torch.float32 by default): with torch.float16 a forward pass that needs no gradient on
+    (B, 1, S, S), S in 128 / 256 / 512, keeps its 32-channel maps and spectral intermediates in IEEE binary16 between the launches
+    (half the memory traffic of whole-slice inference; all arithmetic, the weights, the input and the output stay fp32).  Every
+    other use with torch.float16 set raises NotImplementedError -- there is no silent fp32 pass --, any other value ValueError."""
 
     allow_any_size = False
+    activation_dtype = torch.float32
 
     def __init__(self, in_channels=1, out_channels=96, num_layers=10, kernel_size=5, padding=0):
         super().__init__()
@@ -193,6 +199,8 @@ class ResFFT_Generator(nn.Module):
         _require_cuda(x, "ResFFT_Generator")
         if self._cfg != (1, 32, 10, 3, 1):
             raise NotImplementedError("ResFFT_Generator HIP path is built for MTD_GAN_Method's (1,32,10,3,1) configuration")
+        if self.activation_dtype != torch.float32:
+            return self._forward_half_storage(x)
         any_size = self.allow_any_size and _any_size_ok(x, 1, "ResFFT_Generator", self.parameters())
         if not any_size and (x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != x.shape[3] or x.shape[2] not in (64, 128, 256, 512)):
             raise NotImplementedError(f"ResFFT_Generator HIP path expects (B,1,S,S) with S in 64/128/256/512, got {tuple(x.shape)}")
@@ -204,6 +212,23 @@ class ResFFT_Generator(nn.Module):
             out, _ = GP.generator_forward(xc.reshape(xc.shape[0], xc.shape[2], xc.shape[3], 1), P, False)
             return out.reshape(xc.shape)
         return _GeneratorFn.apply(x.contiguous().float(), self._cfg[2], *self._flat_params())
+
+    def _forward_half_storage(self, x):
+        """activation_dtype = torch.float16: whole-slice inference with binary16 activation storage, or a refusal that names what
+        the mode takes."""
+        if self.activation_dtype != torch.float16:
+            raise ValueError(f"ResFFT_Generator.activation_dtype is torch.float32 or torch.float16, got {self.activation_dtype}")
+        takes = "forward passes without gradients on (B,1,S,S) with S in 128/256/512"
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError(f"ResFFT_Generator with activation_dtype = torch.float16 takes {takes}; this pass needs "
+                                      "gradients (training stays fp32: use torch.no_grad(), or the default activation_dtype)")
+        if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != x.shape[3] or x.shape[2] not in (128, 256, 512):
+            raise NotImplementedError(f"ResFFT_Generator with activation_dtype = torch.float16 takes {takes}, got {tuple(x.shape)} "
+                                      "(64 x 64 patches and the general sizes of allow_any_size are fp32 only)")
+        xc = x.detach().contiguous().float()
+        P = _unflatten_gen([p.detach() for p in self._flat_params()], self._cfg[2])
+        out, _ = GP.generator_forward(xc.reshape(xc.shape[0], xc.shape[2], xc.shape[3], 1), P, False, activation_dtype=torch.float16)
+        return out.reshape(xc.shape)
 
 
 # =================================================================================================

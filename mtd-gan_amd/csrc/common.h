@@ -22,6 +22,49 @@ int mtd_option(int id);
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// ---- storage types of an activation map (binary16 activation storage of whole-slice inference): the kernels that
+// take a storage type as a template parameter compute in fp32 whatever it is; float is the identity, _Float16 converts at the
+// load and rounds to nearest-even at the store (v_cvt_f16_f32 under the default rounding mode; NOT the packed round-toward-zero
+// conversion), clamped to +-65504 first so that a value beyond binary16's range is stored as the largest finite one.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2_st __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ _Float16 st_round(float v) { return (_Float16)__builtin_amdgcn_fmed3f(v, -65504.f, 65504.f); }
+__device__ __forceinline__ f32x4 st_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 st_ld4(const _Float16* p) {
+    const f16x4 h = *reinterpret_cast<const f16x4*>(p);
+    return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+}
+__device__ __forceinline__ void st_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+__device__ __forceinline__ void st_st4(_Float16* p, f32x4 v) {
+    *reinterpret_cast<f16x4*>(p) = f16x4{st_round(v[0]), st_round(v[1]), st_round(v[2]), st_round(v[3])};
+}
+// What a lane keeps in registers between a load and its use: the fp32 vector itself, or the raw words of four / two binary16
+// values -- widened where they are used, so that a prefetch stays a prefetch (a conversion right behind the load would wait for it).
+template <typename ST> struct StWords;
+template <> struct StWords<float> {
+    typedef f32x4 w4;
+    typedef f32x2_st w2;
+    static __device__ __forceinline__ w4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+    static __device__ __forceinline__ f32x4 up4(w4 w) { return w; }
+    static __device__ __forceinline__ f32x2_st up2(w2 w) { return w; }
+    static __device__ __forceinline__ w2 down2(f32x2_st v) { return v; }
+};
+template <> struct StWords<_Float16> {
+    typedef unsigned w4 __attribute__((__vector_size__(8)));
+    typedef unsigned w2;
+    static __device__ __forceinline__ w4 ld4(const _Float16* p) { return *reinterpret_cast<const w4*>(p); }
+    static __device__ __forceinline__ f32x4 up4(w4 w) {
+        const f16x4 h = __builtin_bit_cast(f16x4, w);
+        return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+    }
+    static __device__ __forceinline__ f32x2_st up2(w2 w) {
+        const f16x2 h = __builtin_bit_cast(f16x2, w);
+        return f32x2_st{(float)h[0], (float)h[1]};
+    }
+    static __device__ __forceinline__ w2 down2(f32x2_st v) { return __builtin_bit_cast(w2, f16x2{st_round(v[0]), st_round(v[1])}); }
+};
+
 #define MTD_LAUNCH_CHECK()                      \
     do {                                        \
         hipError_t e__ = hipGetLastError();     \

@@ -240,8 +240,11 @@ __global__ __launch_bounds__(256) void fwd_c1_kernel(const FwdParams p) {
 // PLAIN: no add / mask operands and 16-byte stores (the forward layers): the epilogue is scale, bias, ACT and one store.
 // With the general epilogue in the loop (uniform branches per value for operands that are not there) an iteration
 // was ~190 instructions and a dozen taken branches for 36 FMAs -- the kernel was bound by that, not by its stores.
-template <bool PLAIN, int ACT>
+// OT: the storage type of the output, float or -- PLAIN only, the first layer of whole-slice inference with binary16
+// activation storage -- _Float16 behind a.out: the same sums, rounded to nearest-even at the store.
+template <bool PLAIN, int ACT, typename OT = float>
 __global__ __launch_bounds__(256) void fwd_c1_tile_kernel(const FwdParams p, int R) {
+    static_assert(PLAIN || sizeof(OT) == 4, "the general epilogue stores fp32");
     extern __shared__ float c1tile[];
     const mtd_conv_args& a = p.a;
     const mtd_geom& g = a.g;
@@ -306,7 +309,7 @@ __global__ __launch_bounds__(256) void fwd_c1_tile_kernel(const FwdParams p, int
                 f32x4 q;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) q[j] = apply_act(acc[j] * sc + bias[j], ACT);
-                *reinterpret_cast<f32x4*>(a.out + ((long long)m0 + rx) * a.out_ld + n) = q;
+                st_st4(reinterpret_cast<OT*>(a.out) + ((long long)m0 + rx) * a.out_ld + n, q);
             } else {
                 store_epilogue4(a, acc, sc, bias, (long long)m0 + rx, n, p.vec_store);
             }
@@ -315,6 +318,9 @@ __global__ __launch_bounds__(256) void fwd_c1_tile_kernel(const FwdParams p, int
 }
 
 // N == 1: G = C/4 lanes per pixel, 64/G pixels per wave iteration
+// IT: the storage type of the input, float or _Float16 behind a.in (the last layer of whole-slice inference with
+// binary16 activation storage: its residual operand -- the network's input -- and its output are fp32)
+template <typename IT = float>
 __global__ __launch_bounds__(256) void fwd_n1_kernel(const FwdParams p, int nblk) {
     const mtd_conv_args& a = p.a;
     const mtd_geom& g = a.g;
@@ -345,7 +351,7 @@ __global__ __launch_bounds__(256) void fwd_n1_kernel(const FwdParams p, int nblk
             if (t < p.T) {
                 const int iy = py + p.tap_dy[t], ix = px + p.tap_dx[t];
                 if (live & ((unsigned)iy < (unsigned)g.IH) & ((unsigned)ix < (unsigned)g.IW)) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(a.in + (((long long)b * g.IH + iy) * g.IW + ix) * a.in_ld + 4 * cl);
+                    const f32x4 v = st_ld4(reinterpret_cast<const IT*>(a.in) + (((long long)b * g.IH + iy) * g.IW + ix) * a.in_ld + 4 * cl);
                     acc = fmaf(v[0], w[t][0], acc);
                     acc = fmaf(v[1], w[t][1], acc);
                     acc = fmaf(v[2], w[t][2], acc);
@@ -829,7 +835,7 @@ extern "C" int mtd_conv_direct(const mtd_conv_args* a, void* stream) {
             if (ppb < 4 * PPW) ppb = 4 * PPW;
             p.ppb = (int)ppb;
             const int nblk = (int)((Mpix + ppb - 1) / ppb);
-            hipLaunchKernelGGL(fwd_n1_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, p, nblk);
+            hipLaunchKernelGGL(fwd_n1_kernel<float>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, p, nblk);
         }
         MTD_LAUNCH_CHECK();
         return MTD_OK;
@@ -839,6 +845,72 @@ extern "C" int mtd_conv_direct(const mtd_conv_args* a, void* stream) {
     hipLaunchKernelGGL(direct_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, total, identity);
     MTD_LAUNCH_CHECK();
     return MTD_OK;
+}
+
+// ---- binary16 activation storage: the two ends of the generator on whole slices.  First layer (C == 1): fp32 in,
+// binary16 out on fwd_c1_tile_kernel's PLAIN form; last layer (N == 1): binary16 in, fp32 residual and output on fwd_n1_kernel.
+// The same plans as mtd_conv_direct makes for these layers; what they do not cover is refused, not sent elsewhere.
+extern "C" int mtd_conv_direct_st(const mtd_conv_st_args* sa, void* stream) {
+    if (!sa) return MTD_EINVAL;
+    const mtd_conv_args* a = &sa->a;
+    if (!a->in || !a->w || !a->out || a->out2 || a->act == MTD_ACT_RELU_ADD) return MTD_EINVAL;
+    const mtd_geom& g = a->g;
+    if (a->C <= 0 || a->N <= 0 || g.B <= 0 || g.TH != 3 || g.TW != 3) return MTD_EINVAL;
+    if (a->in_ld < a->C || a->out_ld < a->N) return MTD_EINVAL;
+    const int identity = (g.out_sy == 1 && g.out_sx == 1 && g.out_oy == 0 && g.out_ox == 0 && g.OHF == g.OH && g.OWF == g.OW);
+    const long long Mpix = geom_pixels(g);
+    if (!identity || g.in_sy != 1 || g.in_sx != 1 || g.OH != g.IH || g.OW != g.IW || Mpix >= (1ll << 31)) return MTD_EINVAL;
+    if (a->scale || a->scale2 || a->add2 || a->mask) return MTD_EINVAL;
+    FwdParams p;
+    p.a = *a;
+    p.M = (int)Mpix;
+    p.T = 9;
+    p.identity = 1;
+    p.vec_store = 1;
+    bool seen[9] = {false, false, false, false, false, false, false, false, false};
+    for (int t = 0; t < 9; ++t) {
+        const int ty = t / 3, tx = t % 3;
+        p.tap_dy[t] = ty * g.tap_dy;
+        p.tap_dx[t] = tx * g.tap_dx;
+        p.tap_kidx[t] = (g.ky0 + ty * g.ky_step) * g.KW + (g.kx0 + tx * g.kx_step);
+        const int dy = g.off_y + p.tap_dy[t], dx = g.off_x + p.tap_dx[t];
+        if (dy < -1 || dy > 1 || dx < -1 || dx > 1 || seen[(dy + 1) * 3 + dx + 1]) return MTD_EINVAL;
+        seen[(dy + 1) * 3 + dx + 1] = true;
+    }
+    if (a->C == 1 && sa->in_type == MTD_ST_F32 && sa->out_type == MTD_ST_F16) {
+        if (a->add1 || (a->N % 4) || !is_pow2(a->N / 4) || a->N / 4 > 256) return MTD_EINVAL;
+        if ((a->out_ld % 4) || !aligned16(a->out)) return MTD_EALIGN;
+        p.G = a->N / 4;
+        const int PL = 256 / p.G;
+        if (g.OW % PL) return MTD_EINVAL;
+        p.ppb = PL;                                                        // (the tile kernel does not read it)
+        int R = (int)(((Mpix + 511) / 512) / g.OW);                        // ~512 workgroups of whole image rows, as mtd_conv_direct plans them
+        if (R < 1) R = 1;
+        while (R > 1 && g.OH % R) --R;
+        if ((long long)(R + 2) * (g.OW + 2) * 4 > 48 * 1024) return MTD_EINVAL;
+        const size_t lds = (size_t)(R + 2) * (g.OW + 2) * sizeof(float);
+        const dim3 grid((unsigned)((long long)g.B * g.OH / R));
+        if (a->act == MTD_ACT_LRELU) hipLaunchKernelGGL((fwd_c1_tile_kernel<true, MTD_ACT_LRELU, _Float16>), grid, dim3(256), lds, (hipStream_t)stream, p, R);
+        else if (a->act == MTD_ACT_RELU) hipLaunchKernelGGL((fwd_c1_tile_kernel<true, MTD_ACT_RELU, _Float16>), grid, dim3(256), lds, (hipStream_t)stream, p, R);
+        else if (a->act == MTD_ACT_NONE) hipLaunchKernelGGL((fwd_c1_tile_kernel<true, MTD_ACT_NONE, _Float16>), grid, dim3(256), lds, (hipStream_t)stream, p, R);
+        else return MTD_EINVAL;
+        MTD_LAUNCH_CHECK();
+        return MTD_OK;
+    }
+    if (a->N == 1 && sa->in_type == MTD_ST_F16 && sa->out_type == MTD_ST_F32 && (!a->add1 || sa->add1_type == MTD_ST_F32)) {
+        if ((a->C % 4) || !is_pow2(a->C / 4) || a->C / 4 > 64) return MTD_EINVAL;
+        if ((a->in_ld % 4) || !aligned16(a->in)) return MTD_EALIGN;
+        p.G = a->C / 4;
+        const int PPW = 64 / p.G;
+        long long ppb = (Mpix + 2047) / 2048;
+        if (ppb < 4 * PPW) ppb = 4 * PPW;
+        p.ppb = (int)ppb;
+        const int nblk = (int)((Mpix + ppb - 1) / ppb);
+        hipLaunchKernelGGL(fwd_n1_kernel<_Float16>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, p, nblk);
+        MTD_LAUNCH_CHECK();
+        return MTD_OK;
+    }
+    return MTD_EINVAL;
 }
 
 // called from mtd_conv_wgrad when min(N,C)==1; returns the number of slabs written (or <0)

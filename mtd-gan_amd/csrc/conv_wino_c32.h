@@ -66,9 +66,19 @@ struct C32Params {
 // MASKED2 (round 6: the data-gradient role of the generator's plain 32 -> 32 layers, generator_path.generator_backward): the epilogue's value
 // v goes to a.out2 (where given) and v * (mask > 0 ? 1 : mask_slope) to a.out -- the cotangent and its masked form for the block
 // that consumes it, as the halo-tile kernel writes them (conv_igemm.hip).  Four more 8-byte loads and stores per thread and block.
-template <bool HAS_ADD, bool MASKED2 = false>
+// ST: the storage type of the input, the residual operand and the output -- float, or _Float16 for whole-slice inference
+// with binary16 activation storage (mtd_conv_winograd_st).  Same lane roles: a transform lane loads its four channels with one
+// 8-byte instead of one 16-byte load, an epilogue lane moves its channel pair as one dword; the raw words stay in the prefetch
+// registers and are widened where they are used (row_stage, epi_finish), everything between is fp32 as before.  The a.in /
+// a.add1 / a.out pointers are then binary16 maps behind their float types, the strides count elements.
+template <bool HAS_ADD, bool MASKED2 = false, typename ST = float>
 __global__ __launch_bounds__(512) void wino_c32_kernel(const C32Params cp) {
     constexpr int PX = 6, TWX = 4;
+    constexpr unsigned SB = sizeof(ST);
+    typedef StWords<ST> SW;
+    typedef typename SW::w4 raw4;
+    typedef typename SW::w2 raw2;
+    static_assert(!MASKED2 || SB == 4, "the MASKED2 form (training) is fp32 only");
     __shared__ __attribute__((aligned(16))) float Ls[2 * C32_AS + C32_X];
     float* const Xs = Ls + 2 * C32_AS;
     const WinoParams& wp = cp.wp;
@@ -100,7 +110,7 @@ __global__ __launch_bounds__(512) void wino_c32_kernel(const C32Params cp) {
     const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(MASKED2 ? a.mask : a.in), (short)0, (int)(MASKED2 ? cp.mask_bytes : 0u), 0x00020000);
     const __amdgpu_buffer_rsrc_t o2rs = __builtin_amdgcn_make_buffer_rsrc((MASKED2 && a.out2) ? a.out2 : a.out, (short)0, (int)((MASKED2 && a.out2) ? cp.out2_bytes : 0u), 0x00020000);
     const float mslope = a.mask_slope;
-    const unsigned px_b = (unsigned)a.in_ld * 4u;
+    const unsigned px_b = (unsigned)a.in_ld * SB;
 
     // a thread's tile as (image, tile row, tile column); one step of the walk adds (d_img, d_ty, d_tx) with carries
     struct Cur { int img, ty, tx; };
@@ -123,17 +133,18 @@ __global__ __launch_bounds__(512) void wino_c32_kernel(const C32Params cp) {
     };
     // patch row ti of the tile at c, channels 16 th + 4 tq ..: byte offset of its pixel 0 (formed modulo 2^32: every VALID
     // pixel's offset is in range) and which of its six pixels lie inside the image
-    auto load_patch = [&](f32x4 (&d)[PX], const Cur& c, bool live, int j0, int j1) {
+    auto load_patch = [&](raw4 (&d)[PX], const Cur& c, bool live, int j0, int j1) {
         const int iy = 2 * c.ty - 1 + ti;
         const unsigned p_img = (unsigned)c.img, p_iy = (unsigned)iy;
-        const unsigned pbase = (((p_img * (unsigned)g.IH + p_iy) * (unsigned)g.IW + (unsigned)(TWX * c.tx - 1)) * (unsigned)a.in_ld + (unsigned)(16 * th + 4 * tq)) * 4u;
+        const unsigned pbase = (((p_img * (unsigned)g.IH + p_iy) * (unsigned)g.IW + (unsigned)(TWX * c.tx - 1)) * (unsigned)a.in_ld + (unsigned)(16 * th + 4 * tq)) * SB;
         const bool rv = live & (c.img < g.B) & ((unsigned)iy < (unsigned)g.IH);
         const unsigned pvalid = rv ? (0x3Fu & ~(c.tx == 0 ? 1u : 0u) & ~(c.tx == wp.tiles_x - 1 ? 0x20u : 0u)) : 0u;
 #pragma unroll
         for (int j = j0; j < j1; ++j) {
             const unsigned vo = (pbase + (unsigned)j * px_b) | (((pvalid >> j) & 1u) ? 0u : 0x80000000u);      // (invalid: out of range)
-            if constexpr (!(MTD_C32_SKIP & 8)) d[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 0, 0));
-            else asm volatile("" :: "v"(vo));
+            if constexpr ((MTD_C32_SKIP & 8) != 0) asm volatile("" :: "v"(vo));
+            else if constexpr (SB == 4) d[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ars, vo, 0, 0));
+            else d[j] = __builtin_amdgcn_raw_buffer_load_b64(ars, vo, 0, 0);
         }
     };
     // left pixel of output row ei of the tile at c (-1: no such tile)
@@ -147,14 +158,17 @@ __global__ __launch_bounds__(512) void wino_c32_kernel(const C32Params cp) {
     // Two stages.  row_stage: F(4,3) along the thread's row, r = d B (after it the patch registers are dead: their next request
     // goes out right away and the whole iteration covers its way from memory).  quad_stage: F(2,3) across the quad of lanes that
     // hold the four rows, columns j0 .. j1 - 1, and the stores.
-    auto row_stage = [&](f32x4 (&r)[PX], const f32x4 (&d)[PX]) {
+    auto row_stage = [&](f32x4 (&r)[PX], const raw4 (&dw)[PX]) {
         if constexpr ((MTD_C32_SKIP & 2) != 0) {
 #pragma unroll
             for (int j = 0; j < PX; ++j) {
-                asm volatile("" :: "v"(d[j]));
+                asm volatile("" :: "v"(dw[j]));
                 r[j] = f32x4{1.f, 2.f, 3.f, 4.f};
             }
         } else {
+            f32x4 d[PX];
+#pragma unroll
+            for (int j = 0; j < PX; ++j) d[j] = SW::up4(dw[j]);
             // F(4,3):  B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
             const f32x4 p = d[4] - 4.f * d[2], q = d[3] - 4.f * d[1], u = d[4] - d[2], v = d[3] - d[1];
             r[0] = 4.f * d[0] - 5.f * d[2] + d[4];
@@ -211,14 +225,15 @@ __global__ __launch_bounds__(512) void wino_c32_kernel(const C32Params cp) {
     const float esign = ei ? -1.f : 1.f;
     const int e_off = et * 32 + 4 * ((ecp >> 1) ^ (et & 7)) + 2 * (ecp & 1);
     const int m03_off = (ei ? 3 : 0) * C32_XA;
-    auto load_residual = [&](f32x2 (&e1)[TWX], int epix) {
+    auto load_residual = [&](raw2 (&e1)[TWX], int epix) {
 #pragma unroll
         for (int q = 0; q < TWX; ++q) {
             if constexpr (HAS_ADD) {
-                const unsigned vo = (((unsigned)(epix + q) * (unsigned)a.add1_ld + 2u * (unsigned)ecp) * 4u) | ((unsigned)(epix >> 31) & 0x80000000u);
-                e1[q] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(e1rs, vo, 0, 0));
+                const unsigned vo = (((unsigned)(epix + q) * (unsigned)a.add1_ld + 2u * (unsigned)ecp) * SB) | ((unsigned)(epix >> 31) & 0x80000000u);
+                if constexpr (SB == 4) e1[q] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(e1rs, vo, 0, 0));
+                else e1[q] = __builtin_amdgcn_raw_buffer_load_b32(e1rs, vo, 0, 0);
             } else {
-                e1[q] = f32x2{-0.0f, -0.0f};
+                e1[q] = SW::down2(f32x2{-0.0f, -0.0f});
             }
         }
     };
@@ -249,7 +264,7 @@ __global__ __launch_bounds__(512) void wino_c32_kernel(const C32Params cp) {
             }
         }
     };
-    auto epi_finish = [&](const f32x2 (&t)[PX], const f32x2 (&e1)[TWX], const f32x2 (&mk)[TWX], int epix) {
+    auto epi_finish = [&](const f32x2 (&t)[PX], const raw2 (&e1w)[TWX], const f32x2 (&mk)[TWX], int epix) {
         // A^T of F(4,3) = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
         f32x2 y[TWX];
         const f32x2 s12 = t[1] + t[2], d12 = t[1] - t[2], s34 = t[3] + t[4], d34 = t[3] - t[4];
@@ -259,12 +274,13 @@ __global__ __launch_bounds__(512) void wino_c32_kernel(const C32Params cp) {
         y[3] = d12 + 8.f * d34 + t[5];
 #pragma unroll
         for (int q = 0; q < TWX; ++q) {
+            const f32x2 e1q = SW::up2(e1w[q]);
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 // (slopes in [0, 1]: max(v, slope v) is v for v > 0 and slope v below -- two instructions per activation)
                 float v = y[q][c] + bias2[c];
                 v = fmaxf(v, v * slope_pre);                                           // MTD_ACT_RELU_ADD: the residual AFTER the activation
-                v += e1[q][c];
+                v += e1q[c];
                 y[q][c] = fmaxf(v, v * slope_post);
             }
             if constexpr (MASKED2) {
@@ -273,16 +289,17 @@ __global__ __launch_bounds__(512) void wino_c32_kernel(const C32Params cp) {
 #pragma unroll
                 for (int c = 0; c < 2; ++c) y[q][c] *= mk[q][c] > 0.f ? 1.f : mslope;
             }
-            const unsigned vo = (((unsigned)(epix + q) * (unsigned)a.out_ld + 2u * (unsigned)ecp) * 4u) | ((unsigned)(epix >> 31) & 0x80000000u);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(c32_u32x2, y[q]), ors, vo, 0, 0);
+            const unsigned vo = (((unsigned)(epix + q) * (unsigned)a.out_ld + 2u * (unsigned)ecp) * SB) | ((unsigned)(epix >> 31) & 0x80000000u);
+            if constexpr (SB == 4) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(c32_u32x2, y[q]), ors, vo, 0, 0);
+            else __builtin_amdgcn_raw_buffer_store_b32(SW::down2(y[q]), ors, vo, 0, 0);
         }
     };
 
     // ---- prologue: block 0 transformed into As[0]; blocks 1 and 2 in flight
     Cur curT = cur_init(blk0 * C32_T + tt), curE = cur_init(blk0 * C32_T + et);
     int ld_it = 0;                                       // walk index of the next patch request
-    f32x4 D0[PX], D1[PX];
-    f32x2 E0[TWX], E1[TWX];
+    raw4 D0[PX], D1[PX];
+    raw2 E0[TWX], E1[TWX];
     f32x2 M0[TWX], M1[TWX];
     load_patch(D0, curT, ld_it < nit, 0, PX); cur_step(curT); ++ld_it;
     load_patch(D1, curT, ld_it < nit, 0, PX); cur_step(curT); ++ld_it;
@@ -300,7 +317,7 @@ __global__ __launch_bounds__(512) void wino_c32_kernel(const C32Params cp) {
 
     // One iteration (parity P = it & 1): see the header.  Dn = the patch rows of block it + 1 (then re-requested for it + 3);
     // Ec receives this block's residual operand, Ep holds the previous block's.
-    auto body = [&](auto pc, int it, f32x4 (&Dn)[PX], f32x2 (&Ec)[TWX], const f32x2 (&Ep)[TWX], f32x2 (&Mc)[TWX], const f32x2 (&Mp)[TWX]) {
+    auto body = [&](auto pc, int it, raw4 (&Dn)[PX], raw2 (&Ec)[TWX], const raw2 (&Ep)[TWX], f32x2 (&Mc)[TWX], const f32x2 (&Mp)[TWX]) {
         constexpr int P = decltype(pc)::value;
         const float* Ac = Ls + P * C32_AS;
         float* An = Ls + (P ^ 1) * C32_AS;

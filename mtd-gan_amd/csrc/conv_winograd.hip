@@ -853,6 +853,27 @@ static int wino_fill(const mtd_conv_args* a, const WinoPlan& pl, int pxcode, Win
     return MTD_OK;
 }
 
+// the persistent kernel's walk and buffer extents for operands of `esz` bytes per element (4: fp32; 2: binary16 storage) and its grid
+static C32Params c32_params(const mtd_conv_args& a, const WinoParams& wp, int esz, dim3& pgrid) {
+    C32Params cp;
+    cp.wp = wp;
+    const long long M = wp.p.M;
+    cp.tiles_y = a.g.OH / 2;
+    cp.nblocks = (wp.ntiles + C32_T - 1) / C32_T;
+    cp.out_bytes = (unsigned)(((M - 1) * a.out_ld + a.N) * esz);
+    cp.add_bytes = a.add1 ? (unsigned)(((M - 1) * a.add1_ld + a.N) * esz) : 0u;
+    cp.mask_bytes = a.mask ? (unsigned)(((M - 1) * a.mask_ld + a.N) * esz) : 0u;
+    cp.out2_bytes = a.out2 ? (unsigned)(((M - 1) * a.out2_ld + a.N) * esz) : 0u;
+    const int per = (cp.nblocks + 7) / 8;                    // blocks per XCD; one workgroup per CU: 32 per XCD
+    const int slots = per < 32 ? per : 32;
+    pgrid = dim3(8 * slots);
+    const int step = C32_T * slots;                          // tiles between two blocks of a workgroup's walk
+    cp.d_tx = step % wp.tiles_x;
+    cp.d_ty = (step / wp.tiles_x) % cp.tiles_y;
+    cp.d_img = step / wp.tiles_per_image;
+    return cp;
+}
+
 // a: as for mtd_conv_igemm, except that a->w points to the TRANSFORMED weights of this view and geometry
 // (mtd_winograd_weights; a->w_sn / w_sc / w_st are ignored).  Same epilogue, same split-K workspace contract.
 extern "C" int mtd_conv_winograd(const mtd_conv_args* a, void* stream) {
@@ -872,21 +893,8 @@ extern "C" int mtd_conv_winograd(const mtd_conv_args* a, void* stream) {
     IgemmParams& p = wp.p;
     hipStream_t s = (hipStream_t)stream;
     if (wino_c32_takes(*a, pxcode)) {
-        C32Params cp;
-        cp.wp = wp;
-        cp.tiles_y = a->g.OH / 2;
-        cp.nblocks = (wp.ntiles + C32_T - 1) / C32_T;
-        cp.out_bytes = (unsigned)((((long long)p.M - 1) * a->out_ld + a->N) * 4);
-        cp.add_bytes = a->add1 ? (unsigned)((((long long)p.M - 1) * a->add1_ld + a->N) * 4) : 0u;
-        cp.mask_bytes = a->mask ? (unsigned)((((long long)p.M - 1) * a->mask_ld + a->N) * 4) : 0u;
-        cp.out2_bytes = a->out2 ? (unsigned)((((long long)p.M - 1) * a->out2_ld + a->N) * 4) : 0u;
-        const int per = (cp.nblocks + 7) / 8;                    // blocks per XCD; one workgroup per CU: 32 per XCD
-        const int slots = per < 32 ? per : 32;
-        const dim3 pgrid(8 * slots);
-        const int step = C32_T * slots;                          // tiles between two blocks of a workgroup's walk
-        cp.d_tx = step % wp.tiles_x;
-        cp.d_ty = (step / wp.tiles_x) % cp.tiles_y;
-        cp.d_img = step / wp.tiles_per_image;
+        dim3 pgrid;
+        const C32Params cp = c32_params(*a, wp, 4, pgrid);
         const int prof = mtd_prof_begin(0, a->mask ? (a->add1 ? 33 : 32) : (a->add1 ? 26 : 25), 1, p.M, a->N, a->C, 9, s, algorithmic_bytes(a));
         if (a->mask && a->add1) MTD_LAUNCH((wino_c32_kernel<true, true>), pgrid, dim3(512), 0, s, cp);
         else if (a->mask) MTD_LAUNCH((wino_c32_kernel<false, true>), pgrid, dim3(512), 0, s, cp);
@@ -919,6 +927,41 @@ extern "C" int mtd_conv_winograd(const mtd_conv_args* a, void* stream) {
         else hipLaunchKernelGGL(splitk_epilogue_scalar_kernel, dim3(blocks), dim3(256), 0, s, p);
         MTD_LAUNCH_CHECK();
     }
+    return MTD_OK;
+}
+
+// ---- binary16 activation storage: the generator's 32 -> 32 layers of whole-slice inference on wino_c32_kernel<.., _Float16>.
+// a->a: as for mtd_conv_winograd with in / add1 / out pointing to binary16 maps; exactly the launches the persistent kernel takes in
+// fp32 (wino_c32_takes) without a mask or a second output.  No other kernel has this form: everything else is MTD_EINVAL.
+extern "C" int mtd_conv_winograd_st(const mtd_conv_st_args* sa, void* stream) {
+    if (!sa) return MTD_EINVAL;
+    const mtd_conv_args* a = &sa->a;
+    if (sa->in_type == MTD_ST_F32 && sa->out_type == MTD_ST_F32 && (!a->add1 || sa->add1_type == MTD_ST_F32)) return mtd_conv_winograd(a, stream);
+    if (sa->in_type != MTD_ST_F16 || sa->out_type != MTD_ST_F16 || (a->add1 && sa->add1_type != MTD_ST_F16)) return MTD_EINVAL;
+    if (!mtd_conv_winograd_ok(a)) return MTD_EINVAL;
+    if (!aligned16(a->w)) return MTD_EALIGN;
+    const int pxcode = wino_args_px(*a);
+    if (pxcode != 6 || (a->g.OW % 4) || a->mask || a->out2) return MTD_EINVAL;
+    // (wino_c32_takes asks for 16-byte rows of fp32: strides in multiples of 4 elements and 16-byte bases -- 8-byte rows of binary16 -- and
+    // 31-bit byte offsets at 4 bytes per element: more than this form needs)
+    if (!wino_c32_takes(*a, pxcode)) return MTD_EINVAL;
+    const WinoPlan pl = wino_plan(*a, pxcode);
+    WinoParams wp;
+    {
+        const int rc = wino_fill(a, pl, pxcode, wp);
+        if (rc != MTD_OK) return rc;
+    }
+    wp.p.in_bytes = (unsigned)((((long long)a->g.B * a->g.IH * a->g.IW - 1) * a->in_ld + a->C) * 2);
+    hipStream_t s = (hipStream_t)stream;
+    dim3 pgrid;
+    const C32Params cp = c32_params(*a, wp, 2, pgrid);
+    // (profiler ids 38, 39: wino_c32_kernel<false / true, false, _Float16>)
+    const int prof = mtd_prof_begin(0, a->add1 ? 39 : 38, 1, wp.p.M, a->N, a->C, 9, s,
+                                    0.5 * algorithmic_bytes(a) + 2.0 * 9 * a->N * a->C);      // (the maps at 2 bytes, the weights at 4)
+    if (a->add1) MTD_LAUNCH((wino_c32_kernel<true, false, _Float16>), pgrid, dim3(512), 0, s, cp);
+    else MTD_LAUNCH((wino_c32_kernel<false, false, _Float16>), pgrid, dim3(512), 0, s, cp);
+    mtd_prof_end(prof, s);
+    MTD_LAUNCH_CHECK();
     return MTD_OK;
 }
 

@@ -175,8 +175,12 @@ template <> struct Log2<1> { static constexpr int v = 0; };
 
 // rows forward: a pair of image rows (b, h), (b, h + 1) per step -- the two real rows are the real and imaginary part of one
 // complex transform Z; X_h[k] = (Z[k] + conj Z[-k]) / 2, X_{h+1}[k] = (Z[k] - conj Z[-k]) / 2i.  unit u = b * S/2 + h/2.
-template <int S, int NT>
-__global__ __launch_bounds__(NT) void rfft_rows_any_kernel(const float* __restrict__ x, int x_ld, float* __restrict__ R, int units, int rev) {
+// ST (all three kernels): the storage type of the maps and spectra in memory, float or _Float16.  The lines in LDS, the
+// transforms and the mix are fp32 either way; a lane moves the same four values per access (8 instead of 16 bytes), the prefetched
+// line waits in registers as raw words and is widened on its way into LDS, results are rounded to nearest-even at the store.
+template <int S, int NT, typename ST = float>
+__global__ __launch_bounds__(NT) void rfft_rows_any_kernel(const ST* __restrict__ x, int x_ld, ST* __restrict__ R, int units, int rev) {
+    typedef StWords<ST> SW;
     constexpr int logS = Log2<S>::v, NV = (S * 16 + NT - 1) / NT, nkw = S / 2 + 1;
     extern __shared__ float lds[];
     float* re = lds;
@@ -184,14 +188,14 @@ __global__ __launch_bounds__(NT) void rfft_rows_any_kernel(const float* __restri
     float* tw = lds + S * 64;
     fill_twiddles(tw, S);
     const int tid = threadIdx.x;
-    f32x4 v[NV];
+    typename SW::w4 v[NV];
     auto issue = [&](int u) {
         const int uu = rev ? units - 1 - u : u, b = uu / (S / 2), h = (uu % (S / 2)) * 2;
-        const float* src = x + ((long long)(b * S + h) * S) * x_ld;           // rows h, h + 1: 2 S consecutive pixels
+        const ST* src = x + ((long long)(b * S + h) * S) * x_ld;           // rows h, h + 1: 2 S consecutive pixels
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int q = tid + NT * j, p = q >> 3, c4 = q & 7;
-            if (NV * NT == S * 16 || q < S * 16) v[j] = *reinterpret_cast<const f32x4*>(src + (long long)p * x_ld + c4 * 4);
+            if (NV * NT == S * 16 || q < S * 16) v[j] = SW::ld4(src + (long long)p * x_ld + c4 * 4);
         }
     };
     int u = blockIdx.x;
@@ -200,7 +204,7 @@ __global__ __launch_bounds__(NT) void rfft_rows_any_kernel(const float* __restri
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int q = tid + NT * j, p = q >> 3, c4 = q & 7;
-            if (NV * NT == S * 16 || q < S * 16) *reinterpret_cast<f32x4*>((p >= S ? im : re) + (p & (S - 1)) * 32 + c4 * 4) = v[j];
+            if (NV * NT == S * 16 || q < S * 16) *reinterpret_cast<f32x4*>((p >= S ? im : re) + (p & (S - 1)) * 32 + c4 * 4) = SW::up4(v[j]);
         }
         __syncthreads();
         if (u + (int)gridDim.x < units) issue(u + gridDim.x);                  // lands under this pair's transform
@@ -212,11 +216,11 @@ __global__ __launch_bounds__(NT) void rfft_rows_any_kernel(const float* __restri
             const int pk = brev_n(kw, logS) * 32 + c4 * 4, pm = brev_n((S - kw) & (S - 1), logS) * 32 + c4 * 4;
             const f32x4 zkr = *reinterpret_cast<const f32x4*>(re + pk), zki = *reinterpret_cast<const f32x4*>(im + pk);
             const f32x4 zmr = *reinterpret_cast<const f32x4*>(re + pm), zmi = *reinterpret_cast<const f32x4*>(im + pm);
-            float* o = R + (((long long)(b * nkw + kw) * S + h) * 64) + c4 * 4;
-            *reinterpret_cast<f32x4*>(o) = (zkr + zmr) * sc;
-            *reinterpret_cast<f32x4*>(o + 32) = (zki - zmi) * sc;
-            *reinterpret_cast<f32x4*>(o + 64) = (zki + zmi) * sc;
-            *reinterpret_cast<f32x4*>(o + 96) = (zmr - zkr) * sc;
+            ST* o = R + (((long long)(b * nkw + kw) * S + h) * 64) + c4 * 4;
+            st_st4(o, (zkr + zmr) * sc);
+            st_st4(o + 32, (zki - zmi) * sc);
+            st_st4(o + 64, (zki + zmi) * sc);
+            st_st4(o + 96, (zmr - zkr) * sc);
         }
         __syncthreads();
     }
@@ -237,9 +241,10 @@ __global__ __launch_bounds__(NT) void rfft_rows_any_kernel(const float* __restri
 // 2 056 were nine (the ninth on eight CUs).  A packed unit costs the same MFMAs, two more passes over the column in LDS and two
 // 32 x 32 products on the vector ALU for rows 0 and S/2.  The imaginary halves of columns 0 and S/2 of T are written as zeros.
 constexpr int CLD = 34;        // even (8-byte transform accesses), 2-way bank conflicts for the MFMA operand reads along the frequency index
-template <int S, int NT, bool PACK>
-__global__ __launch_bounds__(NT) void spec_mix_any_kernel(const float* __restrict__ R, const float* __restrict__ w2t,
-                                                           const float* __restrict__ b2, float* __restrict__ T, int units, int rev) {
+template <int S, int NT, bool PACK, typename ST = float>
+__global__ __launch_bounds__(NT) void spec_mix_any_kernel(const ST* __restrict__ R, const float* __restrict__ w2t,
+                                                           const float* __restrict__ b2, ST* __restrict__ T, int units, int rev) {
+    typedef StWords<ST> SW;
     constexpr int logS = Log2<S>::v, NV = (S * 16 + NT - 1) / NT, nkw = S / 2 + 1;
     static_assert(NT % 16 == 0, "a thread keeps its 16-byte part of a spectrum row over a unit");
 #ifdef MTD_ANY_EARLY      /* lab: how many of the next column's NV load vectors go out before the mix / before the forward transform */
@@ -278,14 +283,14 @@ __global__ __launch_bounds__(NT) void spec_mix_any_kernel(const float* __restric
         poff = (PACK && kw == 0 && part >= 8) ? PDELTA : 0;
         return ((long long)(b * nkw + kw) * S) * 64;
     };
-    f32x4 v[NV];
+    typename SW::w4 v[NV];
     auto issue = [&](int un, int j0, int j1) {
         int poff;
-        const float* src = R + unit_base(un, poff);
+        const ST* src = R + unit_base(un, poff);
 #pragma unroll
         for (int j = j0; j < j1; ++j) {
             const int q = tid + NT * j;
-            if (NV * NT == S * 16 || q < S * 16) v[j] = *reinterpret_cast<const f32x4*>(src + (q * 4 + poff));
+            if (NV * NT == S * 16 || q < S * 16) v[j] = SW::ld4(src + (q * 4 + poff));
         }
     };
     int u = blockIdx.x;
@@ -301,7 +306,8 @@ __global__ __launch_bounds__(NT) void spec_mix_any_kernel(const float* __restric
             const int q = tid + NT * j, h = q >> 4;
             if (NV * NT == S * 16 || q < S * 16) {
                 float* d = (part >= 8 ? im : re) + h * CLD + (part & 7) * 4;
-                d[0] = v[j][0]; d[1] = v[j][1]; d[2] = v[j][2]; d[3] = v[j][3];
+                const f32x4 vj = SW::up4(v[j]);
+                d[0] = vj[0]; d[1] = vj[1]; d[2] = vj[2]; d[3] = vj[3];
             }
         }
         __syncthreads();
@@ -448,15 +454,15 @@ __global__ __launch_bounds__(NT) void spec_mix_any_kernel(const float* __restric
         }
         if (!(MTD_ANY_SKIP & 4)) lds_fft<+1, false, CLD, FFT_NT(NT), FFT_UNR, MTD_ANY_FFTV>(re, im, tw, S, logS);
         int poff;
-        float* dstg = T + unit_base(u, poff);
+        ST* dstg = T + unit_base(u, poff);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int q = tid + NT * j, h = q >> 4;
             if (NV * NT == S * 16 || q < S * 16) {
                 const float* d = (part >= 8 ? im : re) + h * CLD + (part & 7) * 4;
                 f32x4 o = {d[0] * sc, d[1] * sc, d[2] * sc, d[3] * sc};
-                *reinterpret_cast<f32x4*>(dstg + (q * 4 + poff)) = o;
-                if (packed) *reinterpret_cast<f32x4*>(dstg + (q * 4 + poff + 32)) = f32x4{0.f, 0.f, 0.f, 0.f};      // (the imaginary halves)
+                st_st4(dstg + (q * 4 + poff), o);
+                if (packed) st_st4(dstg + (q * 4 + poff + 32), f32x4{0.f, 0.f, 0.f, 0.f});      // (the imaginary halves)
             }
         }
         __syncthreads();
@@ -466,10 +472,11 @@ __global__ __launch_bounds__(NT) void spec_mix_any_kernel(const float* __restric
 // rows back (c2r): a pair of image rows per step; out = y + add1 + add2.  With A = X_h, B = X_{h+1} (Hermitian, the imaginary
 // parts of columns 0 and S/2 ignored as torch's c2r does) the complex spectrum Z = A + iB transforms back to row h in the
 // real part and row h + 1 in the imaginary part.
-template <int S, int NT>
-__global__ __launch_bounds__(NT) void irfft_rows_any_kernel(const float* __restrict__ T, float* __restrict__ out, int out_ld,
-                                                              const float* __restrict__ add1, int add1_ld,
-                                                              const float* __restrict__ add2, int add2_ld, int units, int rev) {
+template <int S, int NT, typename ST = float>
+__global__ __launch_bounds__(NT) void irfft_rows_any_kernel(const ST* __restrict__ T, ST* __restrict__ out, int out_ld,
+                                                              const ST* __restrict__ add1, int add1_ld,
+                                                              const ST* __restrict__ add2, int add2_ld, int units, int rev) {
+    typedef StWords<ST> SW;
     constexpr int logS = Log2<S>::v, nkw = S / 2 + 1, NI = (nkw * 8 + NT - 1) / NT, NV = (S * 16 + NT - 1) / NT;
     extern __shared__ float lds[];
     float* re = lds;
@@ -477,18 +484,18 @@ __global__ __launch_bounds__(NT) void irfft_rows_any_kernel(const float* __restr
     float* tw = lds + S * 64;
     fill_twiddles(tw, S);
     const int tid = threadIdx.x;
-    f32x4 t0[NI], t1[NI], t2[NI], t3[NI];
+    typename SW::w4 t0[NI], t1[NI], t2[NI], t3[NI];
     auto issue = [&](int u) {
         const int uu = rev ? units - 1 - u : u, b = uu / (S / 2), h = (uu % (S / 2)) * 2;
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int it = tid + NT * j, kw = it >> 3, c4 = it & 7;
             if (it < nkw * 8) {
-                const float* t = T + (((long long)(b * nkw + kw) * S + h) * 64) + c4 * 4;
-                t0[j] = *reinterpret_cast<const f32x4*>(t);
-                t1[j] = *reinterpret_cast<const f32x4*>(t + 32);
-                t2[j] = *reinterpret_cast<const f32x4*>(t + 64);
-                t3[j] = *reinterpret_cast<const f32x4*>(t + 96);
+                const ST* t = T + (((long long)(b * nkw + kw) * S + h) * 64) + c4 * 4;
+                t0[j] = SW::ld4(t);
+                t1[j] = SW::ld4(t + 32);
+                t2[j] = SW::ld4(t + 64);
+                t3[j] = SW::ld4(t + 96);
             }
         }
     };
@@ -502,7 +509,7 @@ __global__ __launch_bounds__(NT) void irfft_rows_any_kernel(const float* __restr
             if (it < nkw * 8) {
                 const bool edge = (kw == 0 || kw == S / 2);
                 const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                const f32x4 ar = t0[j], ai = edge ? zero : t1[j], br = t2[j], bi = edge ? zero : t3[j];
+                const f32x4 ar = SW::up4(t0[j]), ai = edge ? zero : SW::up4(t1[j]), br = SW::up4(t2[j]), bi = edge ? zero : SW::up4(t3[j]);
                 const int p0 = brev_n(kw, logS) * 32 + c4 * 4;
                 *reinterpret_cast<f32x4*>(re + p0) = ar - bi;
                 *reinterpret_cast<f32x4*>(im + p0) = ai + br;
@@ -521,13 +528,13 @@ __global__ __launch_bounds__(NT) void irfft_rows_any_kernel(const float* __restr
         constexpr int CH = NV < 2 ? NV : 2;                                   // residual operands in chunks: 2 x CH vectors in flight
 #pragma nounroll
         for (int j0 = 0; j0 < NV; j0 += CH) {
-            f32x4 a1[CH], a2[CH];
+            typename SW::w4 a1[CH], a2[CH];
 #pragma unroll
             for (int jj = 0; jj < CH; ++jj) {
                 const int q = tid + NT * (j0 + jj), p = q >> 3, c4 = q & 7;
                 if (NV * NT == S * 16 || q < S * 16) {
-                    if (add1) a1[jj] = *reinterpret_cast<const f32x4*>(add1 + (rowpix + p) * add1_ld + c4 * 4);
-                    if (add2) a2[jj] = *reinterpret_cast<const f32x4*>(add2 + (rowpix + p) * add2_ld + c4 * 4);
+                    if (add1) a1[jj] = SW::ld4(add1 + (rowpix + p) * add1_ld + c4 * 4);
+                    if (add2) a2[jj] = SW::ld4(add2 + (rowpix + p) * add2_ld + c4 * 4);
                 }
             }
 #pragma unroll
@@ -535,9 +542,9 @@ __global__ __launch_bounds__(NT) void irfft_rows_any_kernel(const float* __restr
                 const int q = tid + NT * (j0 + jj), p = q >> 3, c4 = q & 7;
                 if (NV * NT == S * 16 || q < S * 16) {
                     f32x4 o = *reinterpret_cast<const f32x4*>((p >= S ? im : re) + (p & (S - 1)) * 32 + c4 * 4) * sc;
-                    if (add1) o += a1[jj];
-                    if (add2) o += a2[jj];
-                    *reinterpret_cast<f32x4*>(out + (rowpix + p) * out_ld + c4 * 4) = o;
+                    if (add1) o += SW::up4(a1[jj]);
+                    if (add2) o += SW::up4(a2[jj]);
+                    st_st4(out + (rowpix + p) * out_ld + c4 * 4, o);
                 }
             }
         }
@@ -577,50 +584,51 @@ inline int persistent_grid(int units, size_t lds_bytes) {
     return units < g ? units : g;
 }
 
-template <int S>
-int launch_rfft_rows(const float* x, int x_ld, float* R, int B, hipStream_t s) {
+// (profiler ids of class 2: 0 - 2 the fp32 kernels, 3 - 5 their binary16-storage instances)
+template <int S, typename ST>
+int launch_rfft_rows(const ST* x, int x_ld, ST* R, int B, hipStream_t s) {
     const size_t lds = (size_t)S * 256 + (size_t)S * 4;
     constexpr int NT = S >= 512 ? MTD_ANY_NT512 : 1024;
-    int rc = set_lds(rfft_rows_any_kernel<S, NT>, lds);
+    int rc = set_lds(rfft_rows_any_kernel<S, NT, ST>, lds);
     if (rc != MTD_OK) return rc;
     const int units = B * S / 2;
-    const int prof = mtd_prof_begin(2, 0, 1, (long long)B * S * S, 32, 32, 0, s, 4.0 * B * S * 32.0 * (S + 2.0 * (S / 2 + 1)));
-    MTD_LAUNCH((rfft_rows_any_kernel<S, NT>), dim3(persistent_grid(units, lds)), dim3(NT), lds, s, x, x_ld, R, units, any_rev() & 1);
+    const int prof = mtd_prof_begin(2, sizeof(ST) == 4 ? 0 : 3, 1, (long long)B * S * S, 32, 32, 0, s, (double)sizeof(ST) * B * S * 32.0 * (S + 2.0 * (S / 2 + 1)));
+    MTD_LAUNCH((rfft_rows_any_kernel<S, NT, ST>), dim3(persistent_grid(units, lds)), dim3(NT), lds, s, x, x_ld, R, units, any_rev() & 1);
     mtd_prof_end(prof, s);
     return MTD_OK;
 }
 
-template <int S, bool PACK>
-int launch_spec_mix_form(const float* R, const float* w2t, const float* b2, float* T, int B, hipStream_t s) {
+template <int S, bool PACK, typename ST>
+int launch_spec_mix_form(const ST* R, const float* w2t, const float* b2, ST* T, int B, hipStream_t s) {
     const size_t lds = (size_t)2 * S * CLD * 4 + (size_t)S * 4 + (64 * 64 + 64) * 4;
     constexpr int NT = S >= 512 ? MTD_ANY_NT512 : 1024;
-    int rc = set_lds(spec_mix_any_kernel<S, NT, PACK>, lds);
+    int rc = set_lds(spec_mix_any_kernel<S, NT, PACK, ST>, lds);
     if (rc != MTD_OK) return rc;
     const int units = B * (PACK ? S / 2 : S / 2 + 1);
-    const int prof = mtd_prof_begin(2, 1, 1, (long long)B * S * (S / 2 + 1), 64, 64, 0, s, 2.0 * 4.0 * B * S * 64.0 * (S / 2 + 1));
-    MTD_LAUNCH((spec_mix_any_kernel<S, NT, PACK>), dim3(persistent_grid(units, lds)), dim3(NT), lds, s, R, w2t, b2, T, units, (any_rev() >> 1) & 1);
+    const int prof = mtd_prof_begin(2, sizeof(ST) == 4 ? 1 : 4, 1, (long long)B * S * (S / 2 + 1), 64, 64, 0, s, 2.0 * sizeof(ST) * B * S * 64.0 * (S / 2 + 1));
+    MTD_LAUNCH((spec_mix_any_kernel<S, NT, PACK, ST>), dim3(persistent_grid(units, lds)), dim3(NT), lds, s, R, w2t, b2, T, units, (any_rev() >> 1) & 1);
     mtd_prof_end(prof, s);
     return MTD_OK;
 }
 
-template <int S>
-int launch_spec_mix(const float* R, const float* w2t, const float* b2, float* T, int B, hipStream_t s) {
+template <int S, typename ST>
+int launch_spec_mix(const ST* R, const float* w2t, const float* b2, ST* T, int B, hipStream_t s) {
     // (lab library: MTD_ANY_PACK=0 keeps the columns 0 and S/2 as units of their own)
     static const int env_pack = [] { const char* e = mtd_lab_env("MTD_ANY_PACK"); return e ? atoi(e) : 1; }();
-    return env_pack ? launch_spec_mix_form<S, true>(R, w2t, b2, T, B, s) : launch_spec_mix_form<S, false>(R, w2t, b2, T, B, s);
+    return env_pack ? launch_spec_mix_form<S, true, ST>(R, w2t, b2, T, B, s) : launch_spec_mix_form<S, false, ST>(R, w2t, b2, T, B, s);
 }
 
-template <int S>
-int launch_irfft_rows(const float* T, float* out, int out_ld, const float* add1, int add1_ld, const float* add2, int add2_ld, int B,
+template <int S, typename ST>
+int launch_irfft_rows(const ST* T, ST* out, int out_ld, const ST* add1, int add1_ld, const ST* add2, int add2_ld, int B,
                       hipStream_t s) {
     const size_t lds = (size_t)S * 256 + (size_t)S * 4;
     constexpr int NT = S >= 512 ? MTD_ANY_NT512 : 1024;
-    int rc = set_lds(irfft_rows_any_kernel<S, NT>, lds);
+    int rc = set_lds(irfft_rows_any_kernel<S, NT, ST>, lds);
     if (rc != MTD_OK) return rc;
     const int units = B * S / 2;
-    const int prof = mtd_prof_begin(2, 2, 1, (long long)B * S * S, 32, 32, 0, s,
-                                    4.0 * B * S * 32.0 * (2.0 * (S / 2 + 1) + S * (1.0 + (add1 ? 1 : 0) + (add2 ? 1 : 0))));
-    MTD_LAUNCH((irfft_rows_any_kernel<S, NT>), dim3(persistent_grid(units, lds)), dim3(NT), lds, s, T, out, out_ld, add1, add1_ld, add2,
+    const int prof = mtd_prof_begin(2, sizeof(ST) == 4 ? 2 : 5, 1, (long long)B * S * S, 32, 32, 0, s,
+                                    (double)sizeof(ST) * B * S * 32.0 * (2.0 * (S / 2 + 1) + S * (1.0 + (add1 ? 1 : 0) + (add2 ? 1 : 0))));
+    MTD_LAUNCH((irfft_rows_any_kernel<S, NT, ST>), dim3(persistent_grid(units, lds)), dim3(NT), lds, s, T, out, out_ld, add1, add1_ld, add2,
                add2_ld, units, (any_rev() >> 2) & 1);
     mtd_prof_end(prof, s);
     return MTD_OK;
@@ -669,6 +677,55 @@ extern "C" int mtd_irfft_rows_any(const float* T, float* out, int out_ld, const 
                          launch_irfft_rows<128>(T, out, out_ld, add1, add1_ld, add2, add2_ld, B, s),
                          launch_irfft_rows<256>(T, out, out_ld, add1, add1_ld, add2, add2_ld, B, s),
                          launch_irfft_rows<512>(T, out, out_ld, add1, add1_ld, add2, add2_ld, B, s));
+    if (rc != MTD_OK) return rc;
+    MTD_LAUNCH_CHECK();
+    return MTD_OK;
+}
+
+// ---- binary16 storage: the same kernels instantiated for _Float16 maps and spectra, S = 128 / 256 / 512 (the sides of
+// whole-slice inference; the 64 x 64 training patches have kernels of their own and stay fp32)
+#define MTD_BY_SIDE_H(S, CALL128, CALL256, CALL512) ((S) == 128 ? (CALL128) : (S) == 256 ? (CALL256) : (CALL512))
+typedef _Float16 h16;
+
+extern "C" int mtd_rfft_rows_any_h(const void* xv, int x_ld, void* Rv, int B, int S, void* stream) {
+    const h16* x = static_cast<const h16*>(xv);
+    h16* R = static_cast<h16*>(Rv);
+    if (!x || !R || B <= 0 || !(S == 128 || S == 256 || S == 512) || x_ld < 32) return MTD_EINVAL;
+    if ((x_ld % 4) || !aligned16(x) || !aligned16(R)) return MTD_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = MTD_BY_SIDE_H(S, launch_rfft_rows<128>(x, x_ld, R, B, s), launch_rfft_rows<256>(x, x_ld, R, B, s), launch_rfft_rows<512>(x, x_ld, R, B, s));
+    if (rc != MTD_OK) return rc;
+    MTD_LAUNCH_CHECK();
+    return MTD_OK;
+}
+
+extern "C" int mtd_spec_mix_any_h(const void* Rv, const float* w2t, const float* b2, void* Tv, int B, int S, void* stream) {
+    const h16* R = static_cast<const h16*>(Rv);
+    h16* T = static_cast<h16*>(Tv);
+    if (!R || !w2t || !b2 || !T || B <= 0 || !(S == 128 || S == 256 || S == 512)) return MTD_EINVAL;
+    if (!aligned16(R) || !aligned16(T)) return MTD_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = MTD_BY_SIDE_H(S, launch_spec_mix<128>(R, w2t, b2, T, B, s), launch_spec_mix<256>(R, w2t, b2, T, B, s), launch_spec_mix<512>(R, w2t, b2, T, B, s));
+    if (rc != MTD_OK) return rc;
+    MTD_LAUNCH_CHECK();
+    return MTD_OK;
+}
+
+extern "C" int mtd_irfft_rows_any_h(const void* Tv, void* outv, int out_ld, const void* add1v, int add1_ld, const void* add2v,
+                                    int add2_ld, int B, int S, void* stream) {
+    const h16* T = static_cast<const h16*>(Tv);
+    h16* out = static_cast<h16*>(outv);
+    const h16* add1 = static_cast<const h16*>(add1v);
+    const h16* add2 = static_cast<const h16*>(add2v);
+    if (!T || !out || B <= 0 || !(S == 128 || S == 256 || S == 512) || out_ld < 32) return MTD_EINVAL;
+    if ((add1 && add1_ld < 32) || (add2 && add2_ld < 32)) return MTD_EINVAL;
+    if ((out_ld % 4) || !aligned16(T) || !aligned16(out) || (add1 && ((add1_ld % 4) || !aligned16(add1))) ||
+        (add2 && ((add2_ld % 4) || !aligned16(add2))))
+        return MTD_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = MTD_BY_SIDE_H(S, launch_irfft_rows<128>(T, out, out_ld, add1, add1_ld, add2, add2_ld, B, s),
+                           launch_irfft_rows<256>(T, out, out_ld, add1, add1_ld, add2, add2_ld, B, s),
+                           launch_irfft_rows<512>(T, out, out_ld, add1, add1_ld, add2, add2_ld, B, s));
     if (rc != MTD_OK) return rc;
     MTD_LAUNCH_CHECK();
     return MTD_OK;

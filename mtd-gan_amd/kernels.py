@@ -434,7 +434,8 @@ IGEMM_CONFIGS = ["igemm_kernel<2, 1, 4, 1>", "igemm_kernel<1, 1, 4, 1>", "igemm_
                  "wino32_conv_kernel<2, false>", "wino32_conv_kernel<2, true>", "wino32_conv_kernel<4, false>",
                  "wino_c32_kernel<false, true>", "wino_c32_kernel<true, true>",      # 32, 33: ... with a mask operand and a second output (round 6)
                  "wino_conv_multi_kernel<2, false, 6>", "wino_conv_multi_kernel<2, false, 4>", "wino_conv_multi_kernel<4, false, 4>",      # 34-37: two problems of
-                 "wino_conv_multi_kernel<2, true, 4>"]                                                                                         # one shape per launch (round 6)                                                                                       # 29: F(3x3, 2x2) for the 4x4 / stride-2 layers (conv_wino_s2.h)
+                 "wino_conv_multi_kernel<2, true, 4>",
+                 "wino_c32_kernel<false, false, _Float16>", "wino_c32_kernel<true, false, _Float16>"]      # 38, 39: binary16 activation storage (whole-slice inference)                                                                                         # one shape per launch (round 6)                                                                                       # 29: F(3x3, 2x2) for the 4x4 / stride-2 layers (conv_wino_s2.h)
 WGRAD_CONFIGS = ["wgrad_kernel<1, 1, 9>", "wgrad_kernel<1, 1, 4>", "wgrad_kernel<2, 2, 1>", "wgrad_kernel<1, 1, 8>",
                  "wgrad_kernel<1, 1, 3>", "wgrad_kernel<1, 1, 1>", "wgrad_kernel<2, 2, 3>",
                  "wgrad_row_kernel<3, 3, 1>", "wgrad_row_kernel<3, 3, -1>", "wgrad_row_kernel<1, 1, 1>",
@@ -442,7 +443,8 @@ WGRAD_CONFIGS = ["wgrad_kernel<1, 1, 9>", "wgrad_kernel<1, 1, 4>", "wgrad_kernel
                  "wgrad_wino_kernel", "?", "wgrad_wino_s2_kernel", "wgrad_wino32_kernel"]
 
 
-SPECTRAL_KERNELS = ["rfft_rows_any_kernel", "spec_mix_any_kernel", "irfft_rows_any_kernel"]      # profiler class 2 (HBM-bound)
+SPECTRAL_KERNELS = ["rfft_rows_any_kernel", "spec_mix_any_kernel", "irfft_rows_any_kernel",
+                    "rfft_rows_any_kernel<_Float16>", "spec_mix_any_kernel<_Float16>", "irfft_rows_any_kernel<_Float16>"]      # profiler class 2 (HBM-bound)
 
 
 def prof_enable(capacity):
@@ -548,8 +550,10 @@ def ld_of(t):
     return Cc
 
 
-def empty_nhwc(B, H, W, Cc, like):
-    return torch.empty((B, H, W, Cc), dtype=torch.float32, device=like.device)
+def empty_nhwc(B, H, W, Cc, like, dtype=None):
+    """An NHWC map on like's device in like's storage type (fp32, or binary16 inside a whole-slice forward pass with binary16
+    activation storage), or in `dtype` where the map's type differs from its producer's input (the first and the last layer)."""
+    return torch.empty((B, H, W, Cc), dtype=dtype if dtype is not None else like.dtype, device=like.device)
 
 
 # ---------------------------------------------------------------------------------------------- geometry
@@ -605,10 +609,60 @@ def _conv_args(x, w, geom, N, Cc, w_sn, w_sc, out, scale=None, bias=None, add1=N
     return a
 
 
+_ST_OF = {torch.float32: _lib.ST_F32, torch.float16: _lib.ST_F16}
+
+
+def _storage_types(x, out, add1):
+    """(in, add1, out) storage types of a conv launch, or None when all are fp32 (the launch is an ordinary one)."""
+    ts = (x, add1 if add1 is not None else out, out)
+    for t in ts:
+        if t.dtype not in _ST_OF:
+            raise ValueError(f"conv: fp32 or binary16 NHWC maps expected, got {t.dtype}")
+    if all(t.dtype == torch.float32 for t in ts):
+        return None
+    return tuple(_ST_OF[t.dtype] for t in ts)
+
+
+def _conv_st(st, x, w, geom, N, Cc, w_sn, w_sc, out, kw):
+    """conv() with binary16 activation storage: the layers of a whole-slice generator forward pass, each on the one
+    kernel that has the form -- mtd_conv_winograd_st (32 -> 32, all three maps binary16) or mtd_conv_direct_st (1 -> 32: fp32 in,
+    binary16 out; 32 -> 1: binary16 in, fp32 residual and out).  Anything else is an error, never an fp32 launch on converted maps."""
+    L = _lib.lib()
+    takes = winograd_takes(geom, N, Cc, kw)
+    kw = {k: v for k, v in kw.items() if k != "wino32"}
+    for k in ("add2", "mask", "out2", "scale", "scale2"):
+        if kw.get(k) is not None:
+            raise NotImplementedError(f"conv: no binary16-storage kernel takes the operand {k!r}")
+    sa = _lib.ConvStArgs()
+    sa.in_type, sa.add1_type, sa.out_type = st
+    if Cc == 32 and N == 32:
+        a = _conv_args(x, w, geom, N, Cc, w_sn, w_sc, out, pack=False, **kw)
+        if not (takes and L.mtd_conv_winograd_ok(C.byref(a))):
+            raise NotImplementedError(f"conv: binary16 storage is built for the whole-slice 32 -> 32 layers (maps of side >= {WINO_C32_MIN_HW}, "
+                                      f"width a multiple of 4), got {geom.OH} x {geom.OW}")
+        wv, px = winograd_weight_view(w, N, Cc, w_sn, w_sc, geom)      # (the fp32 transformed weights, shared with the fp32 path)
+        a.w, a.w_st = wv.data_ptr(), px
+        if FLOP_COUNT is not None:
+            saved = 2.0 * geom.B * geom.OH * geom.OW * N * Cc * (6 if (px & 15) == 6 else 5)
+            FLOP_COUNT["conv_mfma"] -= saved
+            FLOP_COUNT["conv_winograd_saved"] = FLOP_COUNT.get("conv_winograd_saved", 0.0) + saved
+        sa.a = a
+        check(L.mtd_conv_winograd_st(C.byref(sa), stream_ptr()), "mtd_conv_winograd_st")
+    elif Cc == 1 or N == 1:
+        sa.a = _conv_args(x, w, geom, N, Cc, w_sn, w_sc, out, **kw)
+        check(L.mtd_conv_direct_st(C.byref(sa), stream_ptr()), "mtd_conv_direct_st")
+    else:
+        raise NotImplementedError(f"conv: no binary16-storage kernel for a {Cc} -> {N} channel layer")
+    return out
+
+
 def conv(x, w, geom, N, Cc, w_sn, w_sc, out, **kw):
     """out = epilogue(conv(x, W-view)).  `out` is an NHWC tensor (B, OHF, OWF, >=N view).  Keywords: scale, bias, add1,
     add2, act, mask, mask_slope, scale2, scale_split, out2 (see fuses_masked_cotangent: also store the value before the
-    mask factor)."""
+    mask factor).  The storage types come from x, add1 and out: all fp32, or the binary16 forms of _conv_st."""
+    st = _storage_types(x, out, kw.get("add1"))
+    if st is not None:
+        return _conv_st(st, x, w, geom, N, Cc, w_sn, w_sc, out, kw)
     L = _lib.lib()
     if winograd_s2_takes(geom, N, Cc, kw) and _conv_winograd_s2([((x, w, geom, N, Cc, w_sn, w_sc, out), kw)]):
         return out
@@ -723,6 +777,8 @@ def conv_relu_add_ok(x, w, geom, N, Cc, w_sn, w_sc, out, **kw):
         a = _conv_args(x, w, geom, N, Cc, w_sn, w_sc, out, pack=False, count=False, **kw)
         if _lib.lib().mtd_conv_winograd_ok(C.byref(a)):
             return True
+    if x.dtype != torch.float32:               # (binary16 storage: that kernel or none)
+        return False
     a = _conv_args(x, w, geom, N, Cc, w_sn, w_sc, out, count=False, **kw)
     return bool(_lib.lib().mtd_conv_relu_add_ok(C.byref(a)))
 
@@ -1110,17 +1166,57 @@ def block_tail(x, w, geom, T, img, out, bias=None, act=ACT_RELU):
     return out
 
 
-def spectral_branch_any(x, w2t, b2, out, add1=None, add2=None):
-    """out = add1 + add2 + irfft2(relu(W2 . rfft2(x) + b2)) for a square NHWC map of side 128 / 256 / 512 (forward only)."""
-    L = _lib.lib()
+def _any_entry(name, t):
+    """The whole-slice spectral entry point for t's storage type: fp32, or binary16 (DESIGN 3.3: `name` + "_h", sides 128 / 256 / 512;
+    w2t and b2 stay fp32)."""
+    if t.dtype == torch.float32:
+        return getattr(_lib.lib(), name), name
+    if t.dtype != torch.float16:
+        raise ValueError(f"{name}: fp32 or binary16 maps expected, got {t.dtype}")
+    if t.shape[2] not in (128, 256, 512):
+        raise NotImplementedError(f"{name}: binary16 storage takes sides 128 / 256 / 512, got {t.shape[2]}")
+    return getattr(_lib.lib(), name + "_h"), name + "_h"
+
+
+def _same_storage(name, x, *others):
+    if any(t is not None and t.dtype != x.dtype for t in others):
+        raise ValueError(f"{name}: the maps of one launch share one storage type, got {[x.dtype] + [t.dtype for t in others if t is not None]}")
+
+
+def rfft_rows_any(x):
+    """R = rfft along the rows of a square NHWC map of side 128 / 256 / 512 (64 too in fp32), [B][kw 0..S/2][h][Re 32 | Im 32], in x's
+    storage type."""
     B, S = x.shape[0], x.shape[1]
-    R = torch.empty((B, S // 2 + 1, S, 64), dtype=torch.float32, device=x.device)
+    f, name = _any_entry("mtd_rfft_rows_any", x)
+    R = torch.empty((B, S // 2 + 1, S, 64), dtype=x.dtype, device=x.device)
+    check(f(x.data_ptr(), ld_of(x), R.data_ptr(), B, S, stream_ptr()), name)
+    return R
+
+
+def spec_mix_any(R, w2t, b2):
+    """T = ifft along the columns of relu(W2 . fft along the columns of R + b2), in R's layout and storage type."""
+    B, S = R.shape[0], R.shape[2]
+    f, name = _any_entry("mtd_spec_mix_any", R)
     T = torch.empty_like(R)
-    check(L.mtd_rfft_rows_any(x.data_ptr(), ld_of(x), R.data_ptr(), B, S, stream_ptr()), "mtd_rfft_rows_any")
-    check(L.mtd_spec_mix_any(R.data_ptr(), w2t.data_ptr(), b2.data_ptr(), T.data_ptr(), B, S, stream_ptr()), "mtd_spec_mix_any")
-    check(L.mtd_irfft_rows_any(T.data_ptr(), out.data_ptr(), ld_of(out), _ptr(add1), ld_of(add1) if add1 is not None else 0,
-                               _ptr(add2), ld_of(add2) if add2 is not None else 0, B, S, stream_ptr()), "mtd_irfft_rows_any")
+    check(f(R.data_ptr(), w2t.data_ptr(), b2.data_ptr(), T.data_ptr(), B, S, stream_ptr()), name)
+    return T
+
+
+def irfft_rows_any(T, out, add1=None, add2=None):
+    """out = add1 + add2 + c2r along the rows of T; all maps in T's storage type."""
+    B, S = T.shape[0], T.shape[2]
+    _same_storage("irfft_rows_any", T, out, add1, add2)
+    f, name = _any_entry("mtd_irfft_rows_any", T)
+    check(f(T.data_ptr(), out.data_ptr(), ld_of(out), _ptr(add1), ld_of(add1) if add1 is not None else 0,
+            _ptr(add2), ld_of(add2) if add2 is not None else 0, B, S, stream_ptr()), name)
     return out
+
+
+def spectral_branch_any(x, w2t, b2, out, add1=None, add2=None):
+    """out = add1 + add2 + irfft2(relu(W2 . rfft2(x) + b2)) for a square NHWC map of side 128 / 256 / 512 (forward only).  The
+    storage type -- fp32, or binary16 for the maps and the two spectral intermediates R and T -- is x's."""
+    _same_storage("spectral_branch_any", x, out, add1, add2)
+    return irfft_rows_any(spec_mix_any(rfft_rows_any(x), w2t, b2), out, add1=add1, add2=add2)
 
 
 
