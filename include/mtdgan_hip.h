@@ -446,6 +446,26 @@ int mtd_pcgrad_coeff(const double* gram, const int* orders, int T, float* coeff_
 int mtd_pcgrad_axpy(const float* g0, const float* g1, const float* g2, const float* g3, int T, long long n,
                     const float* coeff, float scale, float* merged, void* stream);
 
+/* ---- the other task weightings of the D step (module/weight_methods.py:275-316, 375-406, 471-588, 591-602, 678-724) ----
+ * mtd_task_weights: one single-wavefront launch turns the T <= 4 device-resident task losses into
+ *   c_out[k]      = d loss / d L_k, the factor the loss cotangents of task k are scaled by (mtd_loss_term.wptr),
+ *   aux_out[0]    = the weighted loss the method returns, aux_out[1 .. 1+T) = the weight vector it reports,
+ *   aux_out[5 .. 5+T) = d loss / d logsigma_k (MTD_TW_UW only).              aux_out: 9 floats.
+ * params: T floats the device can read -- the task weights (LS, SCALEINV), the one-hot vector (STL), the host's normal draw
+ * (RLW: a pinned slot, so that a recorded launch does not bake one draw in); unused by UW / DWA.
+ * state: UW: the T log sigmas (read only).  DWA: mtd_task_weights_state_floats() floats that the kernel owns between calls --
+ * [0] the iteration counter (int bits, starts at 0), [1 .. 5) the weights (start at 1), then the ring of 2 * window rows of T
+ * costs (start at 1); window / temp: DWA's iteration_window and temperature. */
+enum { MTD_TW_LS = 0, MTD_TW_SCALEINV = 1, MTD_TW_STL = 2, MTD_TW_UW = 3, MTD_TW_RLW = 4, MTD_TW_DWA = 5 };
+size_t mtd_task_weights_state_floats(int method, int T, int window);
+int mtd_task_weights(int method, const float* losses, int T, float* state, const float* params, int window, float temp,
+                     float* c_out, float* aux_out, void* stream);
+/* CAGrad (:510-543, :563): from the T x T Gram matrix (T <= 4) of the task gradients the T coefficients of
+ * n_tasks * (mean_k g_k + lambda sum_k ww_k g_k) / (1 + c^2), ww = argmin over the simplex of x^T A b + c0 sqrt(x^T A x + 1e-8),
+ * b = 1/T, c0 = c sqrt(mean(A) + 1e-8) + 1e-8, lambda = c0 / (|sum_k ww_k g_k| + 1e-8).  Exact (stationary point per face of the
+ * simplex, in fp64), fixed work, no host read.  coeff_out: 9 floats -- [0 .. T) the coefficients, [4] phi at ww, [5 .. 5+T) ww. */
+int mtd_cagrad_coeff(const double* gram, int T, float c, float* coeff_out, void* stream);
+
 /* ---- fused multi-tensor AdamW (train.py:122-126; torch.optim.AdamW semantics) ---------------- */
 typedef struct { float* p; const float* g; float* m; float* v; long long n; } mtd_adamw_tensor;
 int mtd_adamw_multi(const mtd_adamw_tensor* tensors_dev, const mtd_adamw_tensor* tensors_host, int count,
@@ -467,6 +487,7 @@ typedef struct {
     const float* mx; const float* my;
     long long n; float scale; float eps;
     float* grad_out; float coef; int accumulate;
+    const float* wptr;      /* optional device-resident factor: the written cotangent is (coef * *wptr) * d term (NULL: coef * d term) */
 } mtd_loss_term;
 size_t mtd_loss_terms_ws_bytes(int nterms);
 int mtd_loss_terms(const void* terms_dev, int nterms, float* out, void* ws, void* stream);

@@ -106,7 +106,7 @@ class MixReduceDesc(C.Structure):
 class LossTerm(C.Structure):
     _fields_ = [("kind", C.c_int), ("a", C.c_void_p), ("b", C.c_void_p), ("tconst", C.c_float),
                 ("mx", C.c_void_p), ("my", C.c_void_p), ("n", C.c_longlong), ("scale", C.c_float), ("eps", C.c_float),
-                ("grad_out", C.c_void_p), ("coef", C.c_float), ("accumulate", C.c_int)]
+                ("grad_out", C.c_void_p), ("coef", C.c_float), ("accumulate", C.c_int), ("wptr", C.c_void_p)]
 
 
 class PtrPair(C.Structure):
@@ -142,7 +142,7 @@ def _preload_torch_hip_runtime():
 
 
 RECORDER = None      # kernels.LaunchList: while a step is being recorded, the list every launch is appended to
-_NOT_LAUNCHES = ("_half_scale_ok", "_pair_ok", "_group_ok", "_ws_bytes", "_blocks", "mtd_version", "_option", "mtd_lab_build", "mtd_prof_", "_override", "_bwd_ok", "_stamps", "_zmask_bytes", "_tail_ok", "_winograd_ok", "_winograd_s2_ok", "_weight_floats", "_kmap", "_plan_cfg", "_pair_ok", "_pair_mode", "_patch_w", "_f4_min_w", "_relu_add_ok")
+_NOT_LAUNCHES = ("_state_floats", "_half_scale_ok", "_pair_ok", "_group_ok", "_ws_bytes", "_blocks", "mtd_version", "_option", "mtd_lab_build", "mtd_prof_", "_override", "_bwd_ok", "_stamps", "_zmask_bytes", "_tail_ok", "_winograd_ok", "_winograd_s2_ok", "_weight_floats", "_kmap", "_plan_cfg", "_pair_ok", "_pair_mode", "_patch_w", "_f4_min_w", "_relu_add_ok")
 
 
 class _RecordingLib:
@@ -306,6 +306,9 @@ def lib():
     sig("mtd_conv_winograd_s2", ci, C.POINTER(ConvArgs), ci, vp)
     sig("mtd_pcgrad_coeff", ci, vp, vp, ci, vp, vp)
     sig("mtd_pcgrad_axpy", ci, vp, vp, vp, vp, ci, ll, vp, cf, vp, vp)
+    sig("mtd_task_weights_state_floats", sz, ci, ci, ci)
+    sig("mtd_task_weights", ci, ci, vp, ci, vp, vp, ci, cf, vp, vp, vp)
+    sig("mtd_cagrad_coeff", ci, vp, ci, cf, vp, vp)
     _lib = L
     return L
 
@@ -322,7 +325,7 @@ EXPORTS = [
     "mtd_spectral_gen_ws_bytes", "mtd_spectral_gen_plan", "mtd_rfft_rows_gen", "mtd_spec_mix_gen", "mtd_irfft_rows_gen",
     "mtd_conv_wgrad_slabs", "mtd_conv_wgrad_slabs_rfft", "mtd_conv_wgrad_reduce_blocks", "mtd_conv_wgrad_reduce_multi", "mtd_spec_mix_wgrad_reduce_multi",
     "mtd_foreground_bbox", "mtd_window_patches", "mtd_hu_window", "mtd_add", "mtd_transpose64_multi", "mtd_upsample2x_bwd_masked",
-    "mtd_prof_mode", "mtd_pcgrad_coeff", "mtd_pcgrad_axpy", "mtd_conv_igemm_multi_ws_bytes", "mtd_conv_igemm_multi",
+    "mtd_prof_mode", "mtd_pcgrad_coeff", "mtd_pcgrad_axpy", "mtd_task_weights_state_floats", "mtd_task_weights", "mtd_cagrad_coeff", "mtd_conv_igemm_multi_ws_bytes", "mtd_conv_igemm_multi",
     "mtd_conv_c32_bwd_ok", "mtd_conv_c32_bwd_ws_bytes", "mtd_conv_c32_bwd",
     "mtd_spec_mix_zmask_bytes", "mtd_spec_mix_fwd4", "mtd_spec_mix_bwd4",
     "mtd_resfft_block_tail_ok", "mtd_resfft_block_tail", "mtd_conv_c32_bwd_irfft",

@@ -78,8 +78,9 @@ __global__ void term_finish_kernel(const mtd_loss_term* __restrict__ T, int nter
 
 __global__ __launch_bounds__(256) void term_grad_kernel(const mtd_loss_term* __restrict__ T) {
     const mtd_loss_term t = T[blockIdx.y];
+    const float coef = t.wptr ? t.coef * *t.wptr : t.coef;       // (a task weight that lives on the device; 1.0f leaves coef's bits)
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < t.n; i += (long long)gridDim.x * 256) {
-        const float g = t.coef * term_grad(t, i);
+        const float g = coef * term_grad(t, i);
         t.grad_out[i] = t.accumulate ? t.grad_out[i] + g : g;
     }
 }

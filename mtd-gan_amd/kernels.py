@@ -1565,7 +1565,8 @@ def loss_term_grads(terms, device):
     check(_lib.lib().mtd_loss_term_grads(tab.data_ptr(), len(terms), stream_ptr()), "mtd_loss_term_grads")
 
 
-def make_term(kind, a, b=None, tconst=0.0, mx=None, my=None, scale=1.0, eps=0.0, grad_out=None, coef=0.0, accumulate=False):
+def make_term(kind, a, b=None, tconst=0.0, mx=None, my=None, scale=1.0, eps=0.0, grad_out=None, coef=0.0, accumulate=False, wptr=None):
+    """wptr: address of one device-resident float the written cotangent is multiplied by as well (a task weight), or None."""
     t = _lib.LossTerm()
     t.kind = kind
     t.a, t.b, t.tconst = a.data_ptr(), (b.data_ptr() if b is not None else None), float(tconst)
@@ -1573,6 +1574,7 @@ def make_term(kind, a, b=None, tconst=0.0, mx=None, my=None, scale=1.0, eps=0.0,
     t.n, t.scale, t.eps = a.numel(), float(scale), float(eps)
     t.grad_out = grad_out.data_ptr() if grad_out is not None else None
     t.coef, t.accumulate = float(coef), 1 if accumulate else 0
+    t.wptr = wptr
     return t
 
 
@@ -1638,6 +1640,25 @@ def pcgrad_axpy(vecs, coeff, scale, merged):
     check(_lib.lib().mtd_pcgrad_axpy(ptrs[0], ptrs[1], ptrs[2], ptrs[3], T, n, coeff.data_ptr(), float(scale), merged.data_ptr(), stream_ptr()),
           "mtd_pcgrad_axpy")
     return merged
+
+
+TW_LS, TW_SCALEINV, TW_STL, TW_UW, TW_RLW, TW_DWA = range(6)      # mtd_task_weights method ids (include/mtdgan_hip.h)
+
+
+def task_weights(method_id, losses, state, params, c_out, aux_out, window=0, temp=1.0):
+    """One launch: the stacked task losses -> c_out[k] = d loss / d L_k, aux_out = [loss, weights[4], d loss / d logsigma[4]].
+    params: a device tensor, or an integer pointer the GPU can dereference (HostScalars.device_ptr()), or None."""
+    pptr = params if (params is None or isinstance(params, int)) else params.data_ptr()
+    check(_lib.lib().mtd_task_weights(int(method_id), losses.data_ptr(), losses.numel(), state.data_ptr() if state is not None else None, pptr,
+                                      int(window), float(temp), c_out.data_ptr(), aux_out.data_ptr(), stream_ptr()), "mtd_task_weights")
+
+
+def cagrad_coeff(gram, T, c):
+    """CAGrad's coefficients from the Gram matrix: a 9-float device tensor, [0:T] the coefficients of the merged gradient,
+    [4] phi at the minimiser, [5:5+T] the minimiser ww."""
+    coeff = torch.empty(9, dtype=torch.float32, device=gram.device)
+    check(_lib.lib().mtd_cagrad_coeff(gram.data_ptr(), int(T), float(c), coeff.data_ptr(), stream_ptr()), "mtd_cagrad_coeff")
+    return coeff
 
 
 def adamw_multi_dyn(params, grads, exp_avg, exp_avg_sq, beta1, beta2, eps, dyn_ptr):

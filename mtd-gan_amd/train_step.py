@@ -67,6 +67,25 @@ class DStepTape:
     def run_pcgrad(self, shared_params, task_specific_params, reduction="sum", dp=None):
         """Per-task backward + PCGrad projection.  Writes .grad of every listed parameter.
         dp: optional data-parallel hook with .all_reduce_avg(flat_tensor) (see parallel.py)."""
+        self._run(shared_params, task_specific_params, reduction, dp, None)
+
+    def run_weighted(self, shared_params, task_specific_params, c, extra_params=()):
+        """A loss weighting (LS, scale-invariant LS, STL, UW, RLW, DWA): the gradient of sum_k c_k L_k.  c: device tensor whose first
+        three floats are the c_k -- every loss cotangent is multiplied by the c_k of its task as it is written, the passes run as for
+        PCGrad, and the three task vectors are added with unit coefficients (no Gram launch).  extra_params: parameters in neither
+        list that the reference's loss.backward() reaches (c_fc): their gradient comes out of the task-specific bucket."""
+        self._run(shared_params, task_specific_params, "sum", None, dict(kind="weighted", c=c, extra=list(extra_params)))
+
+    def run_cagrad(self, shared_params, task_specific_params, c, extra_params=()):
+        """Per-task backward + CAGrad: Gram matrix, mtd_cagrad_coeff, one axpy.  The task-specific parameters (and extra_params:
+        the reference's per-task .backward() calls accumulate into every parameter the graphs reach) get the gradient of the
+        plain sum."""
+        self._run(shared_params, task_specific_params, "sum", None, dict(kind="cagrad", c=float(c), extra=list(extra_params)))
+
+    def _run(self, shared_params, task_specific_params, reduction, dp, spec):
+        """Prepare buffers and seeds -> the passes -> combine.  spec None: PCGrad (the launches of that route do not depend on
+        anything below that reads spec)."""
+        kind = spec["kind"] if spec is not None else "pcgrad"
         D = self.method.Discriminator
         dev = self.x.device
         B = self.x.shape[0]
@@ -74,6 +93,8 @@ class DStepTape:
         by_id = {id(p): nme for nme, p in D.named_parameters()}
         sh_names = [by_id[id(p)] for p in shared_params]
         ts_names = [by_id[id(p)] for p in (task_specific_params or [])]
+        extra_names = [by_id[id(p)] for p in spec["extra"]] if spec is not None else []
+        ts_names = ts_names + extra_names      # (after the listed ones: the bucket's layout for those is the PCGrad route's)
         sizes = [D.get_parameter(nme).numel() for nme in sh_names]
         total = sum(sizes)
         S = torch.empty((4, total), dtype=torch.float32, device=dev)       # 3 task vectors + merged (written whole)
@@ -119,10 +140,11 @@ class DStepTape:
         # ---- the projection order of this step: Python's `random`, as the reference draws it.  Under data parallelism
         # it is a collective decision (rank 0's draw, broadcast on the RCCL stream under the backward passes): ranks with
         # different `random` states would otherwise project the same averaged gradients differently and drift apart.
-        orders = next_orders(3)
-        slot = orders_slot(dev)
-        slot.set([j for o in orders for j in o] + [0] * 7)
-        orders_dev = None
+        orders = orders_dev = slot = None
+        if kind == "pcgrad":
+            orders = next_orders(3)
+            slot = orders_slot(dev)
+            slot.set([j for o in orders for j in o] + [0] * 7)
         if dp is not None:
             orders_dev = dp.broadcast_orders(orders, dev, upload=lambda flat: _upload_slot(slot, dev))
         (re, rd, rr), (fe, fd, fr), (rre, rrd), (rfe, rfd), r12 = self.outs
@@ -140,14 +162,17 @@ class DStepTape:
              "d_rd": h0("d_d"), "d_fd": h1("d_d"), "r_rr": h0("r_r"), "r_fr": h1("r_r"), "c_rd": h0("c_d"), "c_fd": h1("c_d"),
              "c_rrd": h0("c3_d"), "c_rfd": h1("c3_d")}
         T = K.make_term
+        # (a loss weighting: every term times the device-resident c_k of its task -- the prefix of the cotangent's name)
+        wp = {k: (spec["c"].data_ptr() + 4 * i if kind == "weighted" else None) for i, k in enumerate("drc")}
         K.loss_term_grads([
-            T(0, re, tconst=1.0, grad_out=g["d_re"], coef=1.0 / B), T(0, fe, tconst=0.0, grad_out=g["d_fe"], coef=1.0 / B),
-            T(0, rd, tconst=1.0, mx=x, my=y, grad_out=g["d_rd"], coef=1.0 / n), T(0, fd, tconst=0.0, mx=x, my=y, grad_out=g["d_fd"], coef=1.0 / n),
-            T(1, rr, y, grad_out=g["r_rr"], coef=1.0 / n), T(1, fr, fake, grad_out=g["r_fr"], coef=1.0 / n),
-            T(0, re, rre, grad_out=g["c_re"], coef=1.0 / B), T(0, rre, re, grad_out=g["c_rre"], coef=1.0 / B),
-            T(0, rd, rrd, grad_out=g["c_rd"], coef=1.0 / n), T(0, rrd, rd, grad_out=g["c_rrd"], coef=1.0 / n),
-            T(0, fe, rfe, grad_out=g["c_fe"], coef=1.0 / B), T(0, rfe, fe, grad_out=g["c_rfe"], coef=1.0 / B),
-            T(0, fd, rfd, grad_out=g["c_fd"], coef=1.0 / n), T(0, rfd, fd, grad_out=g["c_rfd"], coef=1.0 / n)], dev)
+            T(0, re, tconst=1.0, grad_out=g["d_re"], coef=1.0 / B, wptr=wp["d"]), T(0, fe, tconst=0.0, grad_out=g["d_fe"], coef=1.0 / B, wptr=wp["d"]),
+            T(0, rd, tconst=1.0, mx=x, my=y, grad_out=g["d_rd"], coef=1.0 / n, wptr=wp["d"]),
+            T(0, fd, tconst=0.0, mx=x, my=y, grad_out=g["d_fd"], coef=1.0 / n, wptr=wp["d"]),
+            T(1, rr, y, grad_out=g["r_rr"], coef=1.0 / n, wptr=wp["r"]), T(1, fr, fake, grad_out=g["r_fr"], coef=1.0 / n, wptr=wp["r"]),
+            T(0, re, rre, grad_out=g["c_re"], coef=1.0 / B, wptr=wp["c"]), T(0, rre, re, grad_out=g["c_rre"], coef=1.0 / B, wptr=wp["c"]),
+            T(0, rd, rrd, grad_out=g["c_rd"], coef=1.0 / n, wptr=wp["c"]), T(0, rrd, rd, grad_out=g["c_rrd"], coef=1.0 / n, wptr=wp["c"]),
+            T(0, fe, rfe, grad_out=g["c_fe"], coef=1.0 / B, wptr=wp["c"]), T(0, rfe, fe, grad_out=g["c_rfe"], coef=1.0 / B, wptr=wp["c"]),
+            T(0, fd, rfd, grad_out=g["c_fd"], coef=1.0 / n, wptr=wp["c"]), T(0, rfd, fd, grad_out=g["c_rfd"], coef=1.0 / n, wptr=wp["c"])], dev)
         sink_c = sinks[2]       # the passes run one after the other on one stream pair and all add into the one task-specific bucket
 
         # The decoders' gradients are sums over the tasks that reach them through passes 1+2 (SEG decoder: adversarial +
@@ -230,6 +255,8 @@ class DStepTape:
             dp.all_reduce_avg(TSflat)          # 158 MB, in flight under the Gram / combine kernels; joined below
         # ---- PCGrad: Gram of the original task gradients, replay of the projections, combine
         vecs = [S[0], S[1], S[2]]
+        if kind != "pcgrad":
+            return self._combine_other(spec, vecs, S, shared_params, sizes, task_specific_params, ts_names, extra_names, TSbuf, dev)
         gram = K.pcgrad_gram(vecs)
         if orders_dev is not None:
             coeff = K.pcgrad_combine(vecs, gram, orders_dev, S[3])        # rank 0's order, broadcast at the top of the pass
@@ -250,6 +277,23 @@ class DStepTape:
             dp.wait()
         # (under data parallelism `orders` is this rank's own draw; the order applied is rank 0's, in orders_dev)
         self.gram, self.coeff, self.orders, self.orders_dev, self.task_vectors = gram, coeff, orders, orders_dev, S
+        self.consumed = True
+
+    def _combine_other(self, spec, vecs, S, shared_params, sizes, task_specific_params, ts_names, extra_names, TSbuf, dev):
+        """The combine stage of the loss weightings (unit coefficients: the seeds carried the weights) and of CAGrad."""
+        if spec["kind"] == "weighted":
+            gram, coeff = None, _unit_coeff(dev)
+        else:
+            gram = K.pcgrad_gram(vecs)
+            coeff = K.cagrad_coeff(gram, 3, spec["c"])
+        K.pcgrad_axpy(vecs, coeff, 1.0, S[3])
+        ofs = 0
+        for p, sz in zip(shared_params, sizes):
+            p.grad = S[3, ofs:ofs + sz].view_as(p)
+            ofs += sz
+        for p, nme in zip(list(task_specific_params or []) + list(spec["extra"]), ts_names):
+            p.grad = TSbuf[nme]
+        self.gram, self.coeff, self.orders, self.orders_dev, self.task_vectors = gram, coeff, None, None, S
         self.consumed = True
 
     @staticmethod
@@ -285,6 +329,16 @@ class DStepTape:
 
 _orders_slots = {}
 _pending_orders = []
+_unit_coeffs = {}
+
+
+def _unit_coeff(dev):
+    """(1, 1, 1, 1) on the device, uploaded once per device: the coefficients of a loss weighting's combine launch."""
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    t = _unit_coeffs.get(key)
+    if t is None:
+        t = _unit_coeffs[key] = torch.ones(4, dtype=torch.float32, device=dev)
+    return t
 
 
 def _upload_slot(slot, dev):
@@ -569,9 +623,11 @@ class RecordedTrainStep:
             if self.list.result is None:       # the iteration itself failed: nothing to salvage
                 raise
             raise RecordingUnusable(str(e), *self.list.result) from e
+        from .module.weight_methods import PCGrad
+        self.pcgrad = isinstance(method_D.method, PCGrad)      # (the other replayable methods have no per-iteration host draw)
         try:
             self.slot = orders_slot(dev)
-            if all(self.slot is not sl for sl in self.list.slots):
+            if self.pcgrad and all(self.slot is not sl for sl in self.list.slots):
                 raise RuntimeError("RecordedTrainStep: the recorded iteration did not read the PCGrad order slot")
         except RuntimeError as e:              # the iteration itself is done: do not let the caller run the batch again
             raise RecordingUnusable(str(e), self.names, self.vals) from e
@@ -599,13 +655,31 @@ class RecordedTrainStep:
                       if torch.is_tensor(t)))
 
     @staticmethod
+    def method_refusal(method_D):
+        """Why a step with this task weighting is not recorded (it stays eager), or None.  Replayable: pcgrad with reduction 'sum'
+        and the methods whose per-step state lives in device buffers that the recorded launches read and write in place (ls,
+        scaleinvls, stl, dwa, cagrad)."""
+        from .module import weight_methods as WM
+        if not isinstance(method_D, WM.WeightMethods):
+            return "the task weighting is not a WeightMethods object"
+        m = method_D.method
+        if isinstance(m, WM.PCGrad):
+            return None if m.reduction == "sum" else "pcgrad with reduction 'mean' adds a torch division per step"
+        if isinstance(m, WM.RLW):
+            return "rlw draws its weights on the host every step: a replay would repeat the recorded draw"
+        if isinstance(m, WM.Uncertainty):
+            return "uw trains its log sigmas: their optimizer state is outside what a recorded list checks"
+        if isinstance(m, (WM.LinearScalarization, WM.STL, WM.DynamicWeightAverage, WM.CAGrad)):
+            return None
+        return f"unknown task weighting {type(m).__name__}"
+
+    @staticmethod
     def usable(model, optimizer_G, optimizer_D, method_D, x, y):
         """Can an iteration with these objects be recorded / replayed at all?"""
         from .optimizers import FusedAdamW
-        from .module.weight_methods import PCGrad, WeightMethods
         D = getattr(model, "Discriminator", None)
         return (LIST_MODE and type(model).__name__ == "MTD_GAN_Method" and isinstance(optimizer_G, FusedAdamW) and isinstance(optimizer_D, FusedAdamW)
-                and isinstance(method_D, WeightMethods) and isinstance(method_D.method, PCGrad) and method_D.method.reduction == "sum"
+                and RecordedTrainStep.method_refusal(method_D) is None
                 and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and x.shape == y.shape and tuple(x.shape[1:]) == (1, 64, 64)
                 and not D._inject_masks and torch.is_grad_enabled() and not torch.cuda.is_current_stream_capturing() and not POISON)
 
@@ -620,8 +694,10 @@ class RecordedTrainStep:
             self.x.copy_(x)
             self.y.copy_(y)
         lst = self.list
-        orders = shuffle_orders(3)                                  # this iteration's projection order, drawn as the reference draws it
-        lst.set_slot(self.slot, [j for o in orders for j in o] + [0] * 7)
+        orders = None
+        if self.pcgrad:
+            orders = shuffle_orders(3)                              # this iteration's projection order, drawn as the reference draws it
+            lst.set_slot(self.slot, [j for o in orders for j in o] + [0] * 7)
         self.oD.advance_for_replay(lst.set_slot)
         self.oG.advance_for_replay(lst.set_slot)
         lst.replay()
@@ -662,6 +738,9 @@ def recorded_iteration(model, x, y, optimizer_G, optimizer_D, method_D, dp=None)
     # through kernels.rec; a legacy hook object that only offers all_reduce_avg(flat) keeps its iterations eager)
     if (not RecordedTrainStep.usable(model, optimizer_G, optimizer_D, method_D, x, y)
             or (dp is not None and not (LIST_UNDER_DP and isinstance(dp, parallel.DataParallelSync)))):
+        why = RecordedTrainStep.method_refusal(method_D) if (LIST_MODE and hasattr(method_D, "method")) else None
+        if why is not None and getattr(model, "_mtd_list_error", None) != why:
+            model._mtd_list_error = why             # (reported like every other reason an iteration stays eager)
         return engine.train_iteration(model, x, y, optimizer_G, optimizer_D, method_D, dp)
     st = getattr(model, "_mtd_recorded", None)
     if isinstance(st, RecordedTrainStep):
