@@ -526,6 +526,29 @@ int mtd_window_patches(const short* hu_low, const short* hu_full, int n_slices, 
 /* whole slices (valid / test pipelines, Mayo.py:150-157): out[i] = clip((hu[i] - a_min) / (a_max - a_min), 0, 1) */
 int mtd_hu_window(const short* hu, long long n, float a_min, float a_max, float* out, void* stream);
 
+/* ---- sliding-window inference around a patch predictor (csrc/sliding_window.hip; inferers.py) ---------------------------
+ * The reference evaluates its patch-trained models with monai's sliding_window_inference (engine.py:345,378,835).  Windows
+ * of rh x rw are laid over (B, H, W) single-channel slices: per axis of length `size`, interval iv (1 <= iv <= roi),
+ *     n = ceil((size - roi) / iv) + 1 windows (1 when size == roi),   start(d) = min(d * iv, size - roi);
+ * the global window list runs over images outermost, then window rows, then window columns.  Nothing of it is stored.
+ *   mtd_sw_gather  copies windows [w0, w0 + n) into the contiguous (n, rh, rw) buffer `out` (16-byte vectors where the
+ *                  alignment of a window allows, scalar loads otherwise).
+ *   mtd_sw_blend   acc(B, H, W) += sum over the windows [w0, w0 + n) of map(rh, rw) * pred(n, rh, rw): every covered pixel
+ *                  adds its terms in increasing window index to the value acc holds (fused multiply-add, no atomics), so acc
+ *                  must start as zeros and the chunks must come in order; the bits do not depend on how the list was cut.
+ *                  Only the rows / columns / images that bound the chunk are launched; pixels outside it move no data.
+ *   mtd_sw_finish  out = acc / wsum, wsum = map summed over the windows that cover the pixel (recomputed from the geometry,
+ *                  same order), then clip to [0, 1] if clip01.  out may be acc.
+ * A pixel covered by exactly one window carries that window's prediction through blend and finish unchanged (bit for bit).
+ * MTD_EINVAL: null pointers, size < roi, iv outside 1..roi, a window range outside the list, B * H * W or n * rh * rw >= 2^31,
+ * H or B > 65535. */
+int mtd_sw_gather(const float* in, int B, int H, int W, int rh, int rw, int ivy, int ivx, long long w0, int n, float* out,
+                  void* stream);
+int mtd_sw_blend(const float* pred, const float* map, int B, int H, int W, int rh, int rw, int ivy, int ivx, long long w0, int n,
+                 float* acc, void* stream);
+int mtd_sw_finish(const float* acc, const float* map, int B, int H, int W, int rh, int rw, int ivy, int ivx, int clip01, float* out,
+                  void* stream);
+
 /* ---- backward of one 32 -> 32 channel 3x3 generator layer in ONE launch (csrc/conv_c32_bwd.hip) ----------------------
  * d: the data gradient exactly as mtd_conv_igemm would take it (it must be a launch of the halo-tile kernel: C == N == 32,
  * 3x3, stride 1, 64-pixel rows, whole four-row tiles); w: the weight + bias gradient of the same layer exactly as

@@ -309,6 +309,9 @@ def lib():
     sig("mtd_task_weights_state_floats", sz, ci, ci, ci)
     sig("mtd_task_weights", ci, ci, vp, ci, vp, vp, ci, cf, vp, vp, vp)
     sig("mtd_cagrad_coeff", ci, vp, ci, cf, vp, vp)
+    sig("mtd_sw_gather", ci, vp, ci, ci, ci, ci, ci, ci, ci, ll, ci, vp, vp)
+    sig("mtd_sw_blend", ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, ll, ci, vp, vp)
+    sig("mtd_sw_finish", ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp)
     _lib = L
     return L
 
@@ -334,6 +337,7 @@ EXPORTS = [
     "mtd_set_option", "mtd_get_option", "mtd_lab_build",
     "mtd_winograd_s2_kmap", "mtd_winograd_s2_weights", "mtd_conv_winograd_s2_ok", "mtd_conv_winograd_s2_ws_bytes", "mtd_conv_winograd_s2",
     "mtd_conv_winograd_st", "mtd_conv_direct_st", "mtd_rfft_rows_any_h", "mtd_spec_mix_any_h", "mtd_irfft_rows_any_h",
+    "mtd_sw_gather", "mtd_sw_blend", "mtd_sw_finish",
 ]
 
 

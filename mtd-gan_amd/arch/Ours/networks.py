@@ -59,6 +59,25 @@ def _any_size_ok(x, C, who, params):
     return True
 
 
+def _sliding_window_route(module, x, who):
+    """The opt-in path of sliding_window: None when `module.sliding_window` is unset or x is one roi-sized patch (the caller's
+    usual path then runs -- also for the windows themselves, which come back through forward); otherwise the blended
+    predictions of the module's own patch path over every window of x (inferers.sliding_window_inference)."""
+    sw = module.sliding_window
+    if sw is None:
+        return None
+    from ...inferers import _pair, sliding_window_inference
+    takes = "a dict with roi_size, sw_batch_size and optionally overlap, mode, sigma_scale"
+    if not isinstance(sw, dict) or "roi_size" not in sw or "sw_batch_size" not in sw:
+        raise ValueError(f"{who}.sliding_window is None or {takes}, got {sw!r}")
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters())):
+        raise NotImplementedError(f"{who} with sliding_window set is inference-only: this pass needs gradients (use torch.no_grad(), "
+                                  "or leave sliding_window at None to train on 64 x 64 patches)")
+    if x.dim() != 4 or tuple(x.shape[2:]) == _pair(sw["roi_size"]):
+        return None
+    return sliding_window_inference(x.float(), predictor=module.forward, **sw)
+
+
 class FFT_ConvBlock(nn.Module):
     """x + relu(conv3x3(x)) + irfft2(relu(conv1x1([Re;Im] rfft2(x))))  -- reference networks.py:15-36.
 
@@ -148,10 +167,16 @@ class ResFFT_Generator(nn.Module):
     activation_dtype (class attribute, torch.float32 by default): with torch.float16 a forward pass that needs no gradient on
     (B, 1, S, S), S in 128 / 256 / 512, keeps its 32-channel maps and spectral intermediates in IEEE binary16 between the launches
     (half the memory traffic of whole-slice inference; all arithmetic, the weights, the input and the output stay fp32).  Every
-    other use with torch.float16 set raises NotImplementedError -- there is no silent fp32 pass --, any other value ValueError."""
+    other use with torch.float16 set raises NotImplementedError -- there is no silent fp32 pass --, any other value ValueError.
+
+    sliding_window (class attribute, None by default): a dict of sliding_window_inference's keyword arguments (roi_size,
+    sw_batch_size, overlap, mode) sends a forward pass that needs no gradient on anything but one roi-sized patch through
+    inferers.sliding_window_inference, with this module's own patch path as the predictor -- the generator then sees the
+    64 x 64 maps it was trained on instead of a whole slice.  With it set, a pass that needs gradients raises NotImplementedError."""
 
     allow_any_size = False
     activation_dtype = torch.float32
+    sliding_window = None
 
     def __init__(self, in_channels=1, out_channels=96, num_layers=10, kernel_size=5, padding=0):
         super().__init__()
@@ -199,6 +224,9 @@ class ResFFT_Generator(nn.Module):
         _require_cuda(x, "ResFFT_Generator")
         if self._cfg != (1, 32, 10, 3, 1):
             raise NotImplementedError("ResFFT_Generator HIP path is built for MTD_GAN_Method's (1,32,10,3,1) configuration")
+        windowed = _sliding_window_route(self, x, "ResFFT_Generator")
+        if windowed is not None:
+            return windowed
         if self.activation_dtype != torch.float32:
             return self._forward_half_storage(x)
         any_size = self.allow_any_size and _any_size_ok(x, 1, "ResFFT_Generator", self.parameters())
@@ -477,7 +505,12 @@ class _RedcnnFn(torch.autograd.Function):
 class REDCNN_Generator(nn.Module):
     """Reference networks.py:478-505: 11 conv + 11 conv-transpose (stride 1), additive skips from every encoder INPUT,
     no Res-FFT blocks; every Conv* layer is re-initialised N(0, 0.01) (unlike ResFFT_Generator, whose ConvTranspose2d
-    layers keep PyTorch's default init).  HIP path: the ablation wrappers' configuration (1, 32, 10, 3, 1), 64 x 64 patches."""
+    layers keep PyTorch's default init).  HIP path: the ablation wrappers' configuration (1, 32, 10, 3, 1), 64 x 64 patches.
+
+    sliding_window (class attribute, None by default): as on ResFFT_Generator -- a dict of sliding_window_inference's keyword
+    arguments evaluates whole slices window by window with the 64 x 64 path (inference only)."""
+
+    sliding_window = None
 
     def __init__(self, in_channels=1, out_channels=96, num_layers=10, kernel_size=5, padding=0):
         super().__init__()
@@ -510,6 +543,9 @@ class REDCNN_Generator(nn.Module):
         _require_cuda(x, "REDCNN_Generator")
         if self._cfg != (1, 32, 10, 3, 1):
             raise NotImplementedError("REDCNN_Generator HIP path is built for the ablation wrappers' (1,32,10,3,1) configuration")
+        windowed = _sliding_window_route(self, x, "REDCNN_Generator")
+        if windowed is not None:
+            return windowed
         if x.dim() != 4 or tuple(x.shape[1:]) != (1, 64, 64):
             raise NotImplementedError(f"REDCNN_Generator HIP path expects (B,1,64,64) patches, got {tuple(x.shape)}")
         return _RedcnnFn.apply(x.contiguous().float(), self._cfg[2], *self._flat_params())

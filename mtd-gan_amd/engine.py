@@ -191,7 +191,10 @@ def valid_MTD_GAN_Ours(model, loss, data_loader, device, epoch, save_dir, print_
     Slices may be 64, 128, 256 or 512 pixels square (the reference validates on 512 x 512); with
     `model.Generator.allow_any_size = True`, any H x W with 16 <= H, W <= 512 (cropped slices, other matrix sizes).
     `model.Generator.activation_dtype = torch.float16` runs the 128 / 256 / 512 squares with binary16 activation storage
-    (fp32 arithmetic, input and output; PSNR within 1e-4 dB of the fp32 pass); nothing here changes for it."""
+    (fp32 arithmetic, input and output; PSNR within 1e-4 dB of the fp32 pass); nothing here changes for it.
+    `model.Generator.sliding_window = dict(roi_size=(64, 64), sw_batch_size=..., overlap=..., mode=...)` evaluates each slice
+    window by window instead (the reference's sliding_window_inference calls, engine.py:345): the generator then
+    runs on the 64 x 64 maps it was trained on, and REDCNN_Generator-based models can be evaluated on slices at all."""
     model.Generator.eval()
     model.Discriminator.eval()
     m = _Meter()
@@ -219,7 +222,8 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     clipped prediction) per slice, pred_results.csv.  The perceptual metrics of the reference (PL, TML, FID: torchvision
     VGG16 / InceptionV3 weights) are outside this package; their columns are absent from the result.  Slice sizes as in
     valid_MTD_GAN_Ours (any 16..512 per side with `model.Generator.allow_any_size = True`; the 128 / 256 / 512 squares with
-    binary16 activation storage under `model.Generator.activation_dtype = torch.float16`: predictions and metrics stay fp32)."""
+    binary16 activation storage under `model.Generator.activation_dtype = torch.float16`: predictions and metrics stay fp32;
+    window by window under `model.Generator.sliding_window = dict(...)`)."""
     from . import metrics as M
     model.Generator.eval()
     meters = {}

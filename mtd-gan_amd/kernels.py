@@ -1590,6 +1590,30 @@ def clip01_bwd(g, x):
     return out
 
 
+# ------------------------------------------------------------------------------- sliding-window inference (inferers.py)
+def sw_gather(x, roi, intervals, w0, n, out):
+    """Windows [w0, w0 + n) of the (B, 1, H, W) batch x -> out[:n] of the (>= n, 1, rh, rw) buffer `out`."""
+    B, _, H, W = x.shape
+    check(_lib.lib().mtd_sw_gather(x.data_ptr(), B, H, W, roi[0], roi[1], intervals[0], intervals[1], w0, n, out.data_ptr(), stream_ptr()),
+          "mtd_sw_gather")
+
+
+def sw_blend(pred, imap, acc, roi, intervals, w0, n):
+    """acc (B, 1, H, W) += importance map * predictions of the windows [w0, w0 + n); chunks in order, acc zero at the start."""
+    B, _, H, W = acc.shape
+    check(_lib.lib().mtd_sw_blend(pred.data_ptr(), imap.data_ptr(), B, H, W, roi[0], roi[1], intervals[0], intervals[1], w0, n,
+                                  acc.data_ptr(), stream_ptr()), "mtd_sw_blend")
+
+
+def sw_finish(acc, imap, roi, intervals, clip=False, out=None):
+    """acc / (summed importance of the covering windows), optionally clipped to [0, 1]; in place unless `out` is given."""
+    B, _, H, W = acc.shape
+    out = acc if out is None else out
+    check(_lib.lib().mtd_sw_finish(acc.data_ptr(), imap.data_ptr(), B, H, W, roi[0], roi[1], intervals[0], intervals[1], 1 if clip else 0,
+                                   out.data_ptr(), stream_ptr()), "mtd_sw_finish")
+    return out
+
+
 def edge_loss(a, b, scale, eps=1e-3, grad_out=None, coef=0.0, accumulate=False):
     """a, b: (B,64,64,1) contiguous.  Returns a 1-element tensor scale * sum sqrt(lap(a-b)^2+eps^2)."""
     L = _lib.lib()
