@@ -45,7 +45,7 @@ def _block(i=3):
 
 
 @pytest.mark.parametrize("shape", [(2, 32, 96, 96), (1, 32, 100, 77), (3, 32, 45, 64), (1, 32, 384, 512), (1, 32, 512, 300),
-                                   (1, 32, 509, 509)])
+                                   (1, 32, 509, 509), (1, 32, 49, 112)])
 def test_block_matches_oracle(hip_lib, any_size, shape):
     blk, w = _block()
     x = torch.relu(torch.randn(shape, generator=torch.Generator().manual_seed(sum(shape))))

@@ -203,3 +203,23 @@ def test_spectral_model_matches_torch_irfft2(lib, H, W):
     ref = torch.fft.irfft2(torch.complex(z[:, :32], z[:, 32:]), s=(H, W), dim=(2, 3), norm="ortho").numpy()
     got = _spectral_model(lib, x.numpy(), w2.numpy(), b2.numpy())
     assert np.abs(got - ref).max() < 1e-9 * np.abs(ref).max()
+
+
+def test_stage_test_lengths_cover_every_plan(lib):
+    """The lengths the per-stage GPU test runs (tests/_gen_lengths.py) leave no class of plan out: every radix, every Bluestein
+    convolution length in both parities of n, and every distinct plan (M, radices) the library makes for 16..512."""
+    import _gen_lengths as gl
+    plans = gl.library_plans(lib)
+    assert plans == {n: (plan(lib, n)[0], tuple(plan(lib, n)[1])) for n in range(16, 513)}
+    smooth, blue = gl.select(plans)
+    chosen = smooth + [n for ns in blue.values() for n in ns]
+    assert len(chosen) == len(set(chosen)) and all(16 <= n <= 512 for n in chosen)
+    assert all(plans[n][0] == 0 for n in smooth) and all(plans[n][0] == m for m, ns in blue.items() for n in ns)
+    assert {r for n in smooth for r in plans[n][1]} == {2, 3, 4, 5, 7}
+    assert set(blue) == {64, 128, 256, 512, 1024}
+    for m, ns in blue.items():
+        assert {n % 2 for n in ns} == {0, 1}, (m, ns)
+        of_m = [n for n in plans if plans[n][0] == m]
+        assert min(of_m) in ns and max(of_m) in ns, (m, ns)
+    assert all(n in chosen for n in gl.MODEL_SIDES)
+    assert {plans[n] for n in chosen} == set(plans.values())
