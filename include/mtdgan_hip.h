@@ -305,10 +305,13 @@ int mtd_irfft_rows(const float* T, float* out, int out_ld, const float* add1, in
                    const float* add2, int add2_ld, const float* mask, int mask_ld, int B, void* stream);
 
 /* The same three steps for square maps of side S = 128, 256 or 512 (whole-slice inference, reference engine.py:89,129:
- * the generator runs on 512 x 512 images and rfft2 becomes a 512-point transform).  Forward only; spectra are
- * [B][kw 0..S/2][h 0..S-1][Re 32 | Im 32], ortho scaling 1/sqrt(S) per dimension.  mtd_spec_mix_any writes zeros into the
- * imaginary halves of columns 0 and S/2 of T: mtd_irfft_rows_any does not read them (torch's c2r ignores them too), and the two
- * columns' real parts come out of one packed transform. */
+ * the generator runs on 512 x 512 images and rfft2 becomes a 512-point transform); these fp32 entry points take S = 64 too (an
+ * instantiation of the same kernels, tested like the other sides; the generator sends 64 x 64 maps to the training kernels above).
+ * Any other S is MTD_EINVAL.  Pixel strides are at least 32 floats (MTD_EINVAL) and multiples of 4, all bases 16-byte aligned
+ * (MTD_EALIGN); add1 / add2 may be NULL.  Forward only; spectra are
+ * [B][kw 0..S/2][h 0..S-1][Re 32 | Im 32], ortho scaling 1/sqrt(S) per dimension.  mtd_rfft_rows_any and mtd_spec_mix_any write
+ * exact zeros into the imaginary halves of columns 0 and S/2 of R and T; mtd_spec_mix_any and mtd_irfft_rows_any do not read them
+ * (torch's c2r ignores them too), and the two columns' real parts go through one packed transform each way. */
 int mtd_rfft_rows_any(const float* x, int x_ld, float* R, int B, int S, void* stream);
 int mtd_spec_mix_any(const float* R, const float* w2t, const float* b2, float* T, int B, int S, void* stream);
 int mtd_irfft_rows_any(const float* T, float* out, int out_ld, const float* add1, int add1_ld, const float* add2,

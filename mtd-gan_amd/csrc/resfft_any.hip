@@ -541,8 +541,14 @@ __global__ __launch_bounds__(NT) void irfft_rows_any_kernel(const ST* __restrict
             for (int jj = 0; jj < CH; ++jj) {
                 const int q = tid + NT * (j0 + jj), p = q >> 3, c4 = q & 7;
                 if (NV * NT == S * 16 || q < S * 16) {
-                    f32x4 o = *reinterpret_cast<const f32x4*>((p >= S ? im : re) + (p & (S - 1)) * 32 + c4 * 4) * sc;
-                    if (add1) o += SW::up4(a1[jj]);
+                    // out = fma(y, sc, add1) + add2, the fusing spelled out and none left to the compiler: it fused the scaling into the
+                    // first addition in the fp32 instance and not in the binary16 one, which then rounded another fp32 value than the
+                    // fp32 kernel stores (one fp32 unit of y sc apart: visible where the sum cancels).  The form is the fp32 instance's.
+#pragma clang fp contract(off)
+                    const f32x4 y = *reinterpret_cast<const f32x4*>((p >= S ? im : re) + (p & (S - 1)) * 32 + c4 * 4);
+                    f32x4 o;
+                    if (add1) o = __builtin_elementwise_fma(y, f32x4{sc, sc, sc, sc}, SW::up4(a1[jj]));
+                    else o = y * sc;
                     if (add2) o += SW::up4(a2[jj]);
                     st_st4(out + (rowpix + p) * out_ld + c4 * 4, o);
                 }

@@ -1213,7 +1213,7 @@ def irfft_rows_any(T, out, add1=None, add2=None):
 
 
 def spectral_branch_any(x, w2t, b2, out, add1=None, add2=None):
-    """out = add1 + add2 + irfft2(relu(W2 . rfft2(x) + b2)) for a square NHWC map of side 128 / 256 / 512 (forward only).  The
+    """out = add1 + add2 + irfft2(relu(W2 . rfft2(x) + b2)) for a square NHWC map of side 128 / 256 / 512 (64 too in fp32; forward only).  The
     storage type -- fp32, or binary16 for the maps and the two spectral intermediates R and T -- is x's."""
     _same_storage("spectral_branch_any", x, out, add1, add2)
     return irfft_rows_any(spec_mix_any(rfft_rows_any(x), w2t, b2), out, add1=add1, add2=add2)

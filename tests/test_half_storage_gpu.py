@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mtdgan_oracle as orc  # noqa: E402
 import _half_model as hm  # noqa: E402
-from _metrics import rel  # noqa: E402
+from _metrics import one_rounding as _one_rounding, rel  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 CH = 32
@@ -29,18 +29,6 @@ def _generator():
 
 
 # ------------------------------------------------------------------------------------------------ per launch
-def _one_rounding(name, h, f):
-    """|h - f| <= 2^-11 |f| + 2^-24 for every element: half a unit in the last place of binary16 (relative, and the subnormal floor).
-    No slack for another summation order: every binary16 form is a template instance of the fp32 kernel it is compared with (same
-    lanes, same sums; the storage type only changes the loads' widening and the stores' rounding)."""
-    h, f = h.double().cpu(), f.double().cpu()
-    assert h.shape == f.shape and torch.isfinite(h).all()
-    excess = ((h - f).abs() - (2.0 ** -11 * f.abs() + 2.0 ** -24)).max().item()
-    worst = ((h - f).abs() / (2.0 ** -11 * f.abs() + 2.0 ** -24)).max().item()
-    print(f"{name}: max |h - f| / (2^-11 |f| + 2^-24) = {worst:.4f}, max |f| = {f.abs().max().item():.3f}")
-    assert excess <= 0.0, (name, worst)
-
-
 def _real_activations(S):
     """fp32 maps of a forward pass (encoder.0, the first block, encoder.1, the second block) at side S, as NHWC tensors, and the
     network input: what the layers under test see in a real pass, not uniform noise."""

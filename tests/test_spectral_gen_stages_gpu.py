@@ -20,59 +20,22 @@ import pytest
 import torch
 
 import _gen_lengths as gl
-from _metrics import rel
+import _spectral_stages as ss
+from _spectral_stages import (C, _Report, _cplx, _edges, _mix_reference, _outside_unchanged, _ptr, _randn, _sliced,      # noqa: F401
+                              _tail_unchanged)
 
 pytestmark = pytest.mark.gpu
 
-B, C, LD, OFF = 2, 32, 48, 8
+B = 2
 H_ROWS = 17                   # rows of the row stages: odd, so the last row of each image has no partner
-TAIL = 4096                   # sentinel floats behind R and T
-SENT = 12345.678              # the channels outside a slice
-SPARE_BITS = 0x7FC12345       # the spare image and the floats behind R and T: a quiet NaN with a payload of its own
-BOUND = 1e-5
 N_CHUNKS = 8
 
 CHAIN_PAIRS = [(49, 112), (343, 17), (131, 210), (62, 255), (511, 16), (16, 511)]
 
 
-def _randn(*shape, seed, scale=1.0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float32) * scale
-
-
-def _sliced(v):
-    """v (B, H, W, 32) on the CPU -> (base, view): the view holds v on the device as channels 8..39 of the first B images of a
-    (B + 1, H, W, 48) sentinel tensor; the spare image is NaN."""
-    b, h, w, _ = v.shape
-    base = torch.full((b + 1, h, w, LD), SENT, dtype=torch.float32, device="cuda")
-    base[b].view(torch.int32).fill_(SPARE_BITS)
-    view = base[:b, :, :, OFF:OFF + C]
-    view.copy_(v)
-    return base, view
-
-
-def _outside_unchanged(base):
-    """The sentinel channels and the spare image of a sliced map, bit for bit."""
-    bits = base.view(torch.int32)
-    want = torch.tensor(SENT, dtype=torch.float32).view(torch.int32).item()
-    return bool((bits[:-1, :, :, :OFF] == want).all() and (bits[:-1, :, :, OFF + C:] == want).all()
-                and (bits[-1] == SPARE_BITS).all())
-
-
 def _spectrum(nkw, h, fill=None):
     """(flat, S): S = the first B nkw h 64 floats of flat as [B][nkw][h][Re 32 | Im 32]; TAIL sentinel floats follow."""
-    n = B * nkw * h * 64
-    flat = torch.empty((n + TAIL,), dtype=torch.float32, device="cuda")
-    flat[n:].view(torch.int32).fill_(SPARE_BITS)
-    S = flat[:n].view(B, nkw, h, 64)
-    if fill is not None:
-        S.copy_(fill)
-    else:
-        S.fill_(float("nan"))
-    return flat, S
-
-
-def _tail_unchanged(flat):
-    return bool((flat[-TAIL:].view(torch.int32) == SPARE_BITS).all())
+    return ss._spectrum(B, nkw, h, fill)
 
 
 def _nan_workspace(K, L, h, w):
@@ -81,47 +44,6 @@ def _nan_workspace(K, L, h, w):
     ws = K.workspace(need, torch.device("cuda", torch.cuda.current_device()))
     ws[:ws.numel() // 4 * 4].view(torch.float32).fill_(float("nan"))
     return ws
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _cplx(S):
-    """[..., Re 32 | Im 32] float32 -> complex128 on the CPU."""
-    S = S.detach().cpu().double()
-    return torch.complex(S[..., :C].contiguous(), S[..., C:].contiguous())
-
-
-def _edges(w):
-    return [0] + ([w // 2] if w % 2 == 0 else [])
-
-
-class _Report:
-    """Worst error per stage of one test item, and what failed."""
-
-    def __init__(self):
-        self.worst, self.fails = {}, []
-
-    def err(self, stage, case, got, ref):
-        e = rel(got, ref)
-        if not e <= self.worst.get(stage, (-1.0, None))[0]:          # (a NaN error is kept too)
-            self.worst[stage] = (e, case)
-        if not e < BOUND:
-            d = (torch.as_tensor(got).double().cpu() - torch.as_tensor(ref).double().cpu()).abs()
-            at = tuple(int(i) for i in torch.unravel_index(d.argmax(), d.shape))
-            self.fails.append(f"{stage} {case}: rel {e:.3e}, largest difference at {at}")
-
-    def check(self, ok, stage, case, what):
-        if not ok:
-            self.fails.append(f"{stage} {case}: {what}")
-
-    def finish(self, record_property):
-        text = ", ".join(f"{s} {e:.3e} at {c}" for s, (e, c) in sorted(self.worst.items()))
-        for s, (e, c) in self.worst.items():
-            record_property(f"worst_{s}", f"{e:.3e} at {c}")
-        print(f"\nworst rel per stage: {text}")
-        assert not self.fails, f"worst rel per stage: {text}; failed: " + "; ".join(self.fails)
 
 
 # ------------------------------------------------------------------------------------------------------------- stages
@@ -141,17 +63,6 @@ def _rows_forward(K, L, rep, n):
     rep.err("rows_im", n, got[..., C:], ref.imag)
     rep.check(_tail_unchanged(flat), "rows", n, "the floats behind R changed")
     rep.check(torch.equal(xb.view(torch.int32), keep.view(torch.int32)), "rows", n, "the input map changed")
-
-
-def _mix_reference(Rin, w2, b2, w):
-    """T = ifft_H(relu(W2 [Re; Im](fft_H(R)) + b2)), both ortho, the imaginary halves of column 0 and (even W) W/2 exactly 0."""
-    X = torch.fft.fft(_cplx(Rin), dim=2, norm="ortho")
-    cat = torch.cat([X.real, X.imag], dim=-1)                                            # (B, nkw, H, 64)
-    y = torch.relu(cat @ w2.double().t() + b2.double())
-    T = torch.fft.ifft(torch.complex(y[..., :C].contiguous(), y[..., C:].contiguous()), dim=2, norm="ortho")
-    ref = torch.cat([T.real, T.imag], dim=-1)
-    ref[:, _edges(w), :, C:] = 0.0
-    return ref
 
 
 def _columns_mix(K, L, rep, n, w2, b2, w2t, b2d):
