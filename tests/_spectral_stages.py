@@ -1,5 +1,6 @@
 """What the per-stage tests of the spectral kernels share (test_spectral_gen_stages_gpu.py: the general lengths, csrc/resfft_gen.hip;
-test_spectral_pow2_stages_gpu.py: the power-of-two squares, csrc/resfft_any.hip): maps as channel slices of sentinel tensors, spectra
+test_spectral_pow2_stages_gpu.py: the power-of-two squares, csrc/resfft_any.hip; test_spectral_train_stages_gpu.py: the 64 x 64
+training kernels, csrc/resfft.hip and resfft4.hip): maps as channel slices of sentinel tensors, spectra
 with sentinel floats behind them, the float64 reference of the column stage and the report of the worst error per stage.
 
 Every map is a 32-channel slice (channel offset 8) of a 48-channel NHWC tensor whose other channels hold a sentinel, with one spare
@@ -30,22 +31,22 @@ def _spare(dtype):
     return SPARE_BITS if dtype == torch.float32 else SPARE_BITS_H
 
 
-def _sliced(v, dtype=torch.float32):
+def _sliced(v, dtype=torch.float32, ld=LD, off=OFF):
     """v (B, H, W, 32) on the CPU -> (base, view): the view holds v on the device as channels 8..39 of the first B images of a
-    (B + 1, H, W, 48) sentinel tensor; the spare image is NaN."""
+    (B + 1, H, W, 48) sentinel tensor; the spare image is NaN.  (ld, off: another pixel stride and channel offset.)"""
     b, h, w, _ = v.shape
-    base = torch.full((b + 1, h, w, LD), SENT, dtype=dtype, device="cuda")
+    base = torch.full((b + 1, h, w, ld), SENT, dtype=dtype, device="cuda")
     _bits(base[b]).fill_(_spare(dtype))
-    view = base[:b, :, :, OFF:OFF + C]
+    view = base[:b, :, :, off:off + C]
     view.copy_(v)
     return base, view
 
 
-def _outside_unchanged(base):
+def _outside_unchanged(base, off=OFF):
     """The sentinel channels and the spare image of a sliced map, bit for bit."""
     bits = _bits(base)
     want = _bits(torch.tensor(SENT, dtype=base.dtype)).item()
-    return bool((bits[:-1, :, :, :OFF] == want).all() and (bits[:-1, :, :, OFF + C:] == want).all()
+    return bool((bits[:-1, :, :, :off] == want).all() and (bits[:-1, :, :, off + C:] == want).all()
                 and (bits[-1] == _spare(base.dtype)).all())
 
 
@@ -84,15 +85,29 @@ def _edges(w):
     return [0] + ([w // 2] if w % 2 == 0 else [])
 
 
-def _mix_reference(Rin, w2, b2, w):
-    """T = ifft_H(relu(W2 [Re; Im](fft_H(R)) + b2)), both ortho, the imaginary halves of column 0 and (even W) W/2 exactly 0."""
+def _mix_stages(Rin, w2, b2):
+    """(S, Z, T) in float64, each (B, nkw, H, [Re 32 | Im 32]): S = fft_H(R), Z = [Re; Im]S W2^T + b2, T = ifft_H(relu Z), both
+    ortho; T is the full complex result.  Differentiable in w2 and b2 when they are float64 leaves."""
     X = torch.fft.fft(_cplx(Rin), dim=2, norm="ortho")
     cat = torch.cat([X.real, X.imag], dim=-1)                                            # (B, nkw, H, 64)
-    y = torch.relu(cat @ w2.double().t() + b2.double())
+    z = cat @ w2.double().t() + b2.double()
+    y = torch.relu(z)
     T = torch.fft.ifft(torch.complex(y[..., :C].contiguous(), y[..., C:].contiguous()), dim=2, norm="ortho")
-    ref = torch.cat([T.real, T.imag], dim=-1)
+    return cat, z, torch.cat([T.real, T.imag], dim=-1)
+
+
+def _mix_reference(Rin, w2, b2, w):
+    """T = ifft_H(relu(W2 [Re; Im](fft_H(R)) + b2)), both ortho, the imaginary halves of column 0 and (even W) W/2 exactly 0."""
+    ref = _mix_stages(Rin, w2, b2)[2]
     ref[:, _edges(w), :, C:] = 0.0
     return ref
+
+
+def _back_reference(Tin, S):
+    """c2r along W of T with the imaginary halves of the columns 0 and S/2 taken as zero, (B, S, S, 32) in float64."""
+    Tc = _cplx(Tin)
+    Tc.imag[:, [0, S // 2]] = 0.0
+    return torch.fft.irfft(Tc.permute(0, 2, 3, 1), n=S, dim=3, norm="ortho").permute(0, 1, 3, 2)
 
 
 class _Report:

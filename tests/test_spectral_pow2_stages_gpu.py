@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from _metrics import one_rounding
-from _spectral_stages import (C, _Report, _bits, _cplx, _mix_reference, _outside_unchanged, _ptr, _randn, _same_bits, _sliced,
+from _spectral_stages import (C, _Report, _back_reference, _bits, _mix_reference, _outside_unchanged, _ptr, _randn, _same_bits, _sliced,
                               _spectrum, _tail_unchanged)
 
 pytestmark = pytest.mark.gpu
@@ -91,13 +91,6 @@ def _mix_input(S, B):
 def _edge_halves_set(t, value):
     t[:, 0, :, C:] = value
     t[:, t.shape[1] - 1, :, C:] = value
-
-
-def _back_reference(Tin, S):
-    """c2r along W of T with the imaginary halves of the columns 0 and S/2 taken as zero, (B, S, S, 32) in float64."""
-    Tc = _cplx(Tin)
-    Tc.imag[:, [0, S // 2]] = 0.0
-    return torch.fft.irfft(Tc.permute(0, 2, 3, 1), n=S, dim=3, norm="ortho").permute(0, 1, 3, 2)
 
 
 # --------------------------------------------------------------------------------------------------------- fp32 stages
