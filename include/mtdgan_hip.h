@@ -511,6 +511,30 @@ int mtd_edge_loss(const float* a, const float* b, int B, float scale, float eps,
 size_t mtd_image_metrics_ws_bytes(int B, int H, int W);
 int mtd_image_metrics(const float* a, const float* b, int B, int H, int W, int clip_a, double* out2, void* ws, void* stream);
 
+/* ---- perceptual metrics of the test loop (metrics.py:43-168: PL and TML on VGG-19 features; engine.py:139-140) ------
+ * The convolutions of the feature stack are mtd_conv_* launches; these are the other pieces.  Maps are contiguous NHWC fp32,
+ * 16-byte aligned (MTD_EALIGN).
+ *   mtd_maxpool2x2        nn.MaxPool2d(2, 2): out (B, H/2, W/2, C) from in (B, H, W, C), floor semantics (an odd last row or
+ *                         column is dropped), NaN propagates as in torch.  Any B >= 1, H, W >= 2, C a multiple of 4 (else
+ *                         MTD_EINVAL).  One float4 of channels per thread and round; at most MTD_MAXPOOL_MAX_BLOCKS workgroups
+ *                         of 256 threads, so maps of more than 256 * MTD_MAXPOOL_MAX_BLOCKS output float4 take further rounds.
+ *   mtd_patch_gram_l1     X, Y (B, h, w, C), C in {64, 128, 256, 512}.  Over the non-overlapping 16 x 16 patches ((h/16) * (w/16) per
+ *                         image; remainder rows / columns are never read) with G(F) = sum over the patch's 256 pixels of f f^T
+ *                         (C x C, not normalised): out[0] = sum over patches and all C^2 entries of |G(X) - G(Y)|, in double.
+ *                         The mean of nn.L1Loss is out[0] / (B * patches * C^2).  fp32 MFMA products; the reduction has a fixed
+ *                         order (per-workgroup partials in ws, mtd_patch_gram_l1_ws_bytes(B, h, w, C) bytes, then one finishing
+ *                         pass), and X, Y run through the same instructions: X == Y gives exactly 0.  No patch (h or w < 16), any
+ *                         other C, null pointers: MTD_EINVAL (the _ws_bytes query then returns 0).
+ *   mtd_scaled_sums_f64   out[g] = (float) sum_{i < per} scales_host[i] * in[g * per + i] for g < groups: the weighted sum over
+ *                         the five feature levels of several loss values at once.  per <= MTD_SCALED_SUMS_MAX; scales_host is
+ *                         read on the host during the call. */
+#define MTD_MAXPOOL_MAX_BLOCKS 2048
+#define MTD_SCALED_SUMS_MAX 8
+int mtd_maxpool2x2(const float* in, float* out, int B, int H, int W, int C, void* stream);
+size_t mtd_patch_gram_l1_ws_bytes(int B, int h, int w, int C);
+int mtd_patch_gram_l1(const float* X, const float* Y, int B, int h, int w, int C, double* out, void* ws, void* stream);
+int mtd_scaled_sums_f64(const double* in, int groups, int per, const double* scales_host, float* out, void* stream);
+
 /* ---- training-patch front end (create_datasets/Mayo.py:117-136, the "window_patch" pipeline, on the device) ----------
  * Input: the two dose levels of one or more CT slices in Hounsfield units as the reference's get_pixels_hu produces them
  * (int16, Mayo.py:19-43), resident in HBM.  mtd_foreground_bbox = CropForegroundd(source_key = full dose, select x > 0

@@ -273,6 +273,10 @@ def lib():
     sig("mtd_edge_loss_ws_bytes", sz, ci)
     sig("mtd_image_metrics_ws_bytes", sz, ci, ci, ci)
     sig("mtd_image_metrics", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
+    sig("mtd_maxpool2x2", ci, vp, vp, ci, ci, ci, ci, vp)
+    sig("mtd_patch_gram_l1_ws_bytes", sz, ci, ci, ci, ci)
+    sig("mtd_patch_gram_l1", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
+    sig("mtd_scaled_sums_f64", ci, vp, ci, ci, C.POINTER(C.c_double), vp, vp)
     sig("mtd_edge_loss", ci, vp, vp, ci, cf, cf, vp, vp, cf, ci, vp, vp)
     sig("mtd_foreground_bbox", ci, vp, ci, ci, ci, cf, vp, vp)
     sig("mtd_window_patches", ci, vp, vp, ci, ci, ci, vp, vp, ci, cf, cf, ci, vp, vp, vp)
@@ -338,6 +342,7 @@ EXPORTS = [
     "mtd_winograd_s2_kmap", "mtd_winograd_s2_weights", "mtd_conv_winograd_s2_ok", "mtd_conv_winograd_s2_ws_bytes", "mtd_conv_winograd_s2",
     "mtd_conv_winograd_st", "mtd_conv_direct_st", "mtd_rfft_rows_any_h", "mtd_spec_mix_any_h", "mtd_irfft_rows_any_h",
     "mtd_sw_gather", "mtd_sw_blend", "mtd_sw_finish",
+    "mtd_maxpool2x2", "mtd_patch_gram_l1_ws_bytes", "mtd_patch_gram_l1", "mtd_scaled_sums_f64",
 ]
 
 

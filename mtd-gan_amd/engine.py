@@ -218,14 +218,18 @@ def valid_MTD_GAN_Ours(model, loss, data_loader, device, epoch, save_dir, print_
 
 @torch.no_grad()
 def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
-    """Mirror of engine.py:108-183 for the pixel metrics: whole-slice inference, L1, RMSE / PSNR / SSIM of (input, gt,
-    clipped prediction) per slice, pred_results.csv.  The perceptual metrics of the reference (PL, TML, FID: torchvision
-    VGG16 / InceptionV3 weights) are outside this package; their columns are absent from the result.  Slice sizes as in
-    valid_MTD_GAN_Ours (any 16..512 per side with `model.Generator.allow_any_size = True`; the 128 / 256 / 512 squares with
+    """Mirror of engine.py:108-183: whole-slice inference, L1, RMSE / PSNR / SSIM of (input, gt, clipped prediction) per slice,
+    pred_results.csv.  The perceptual metrics PL and TML (engine.py:139-140, VGG-19 features) are computed when the model carries
+    the feature network: `model.perceptual_vgg = metrics.VGG19Features(state_dict)` -- the torchvision `vgg19` checkpoint is the
+    caller's to hand over, none ships with this package.  The result then gains input_pl / gt_pl / pred_pl / input_tml / gt_tml /
+    pred_tml and the CSV the reference's PL and TML columns (slices of at least 256 x 256: metrics.compute_TML); without the
+    attribute (or with None) the keys and the CSV are those of the pixel metrics alone.  FID (InceptionV3) is outside this
+    package.  Slice sizes as in valid_MTD_GAN_Ours (any 16..512 per side with `model.Generator.allow_any_size = True`; the 128 / 256 / 512 squares with
     binary16 activation storage under `model.Generator.activation_dtype = torch.float16`: predictions and metrics stay fp32;
     window by window under `model.Generator.sliding_window = dict(...)`)."""
     from . import metrics as M
     model.Generator.eval()
+    vgg = getattr(model, "perceptual_vgg", None)
     meters = {}
     rows = []
     for batch_data in data_loader:
@@ -234,17 +238,25 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
         pred = model.Generator(x)
         meters.setdefault("L1_loss", _Meter()).update(float(_l1(loss, pred, y)), 1)
         from . import kernels as K
-        pm = M.pixel_metrics(x, y, K.clip01(pred.contiguous()))
+        clipped = K.clip01(pred.contiguous())
+        perceptual = ()
+        if vgg is not None:
+            six = M.perceptual_metrics(x, y, clipped, vgg).tolist()        # the slice's six values in one device -> host copy
+            for j, name in enumerate(("pl", "tml")):
+                for who, v in zip(("input", "gt", "pred"), six[3 * j:3 * j + 3]):
+                    meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+            perceptual = (six[2], six[5])
+        pm = M.pixel_metrics(x, y, clipped)
         for name, triple in pm.items():
             for who, v in zip(("input", "gt", "pred"), triple):
                 meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
         path = batch_data.get("path_n_20", [f"slice_{len(rows)}"])[0] if isinstance(batch_data, dict) else f"slice_{len(rows)}"
-        rows.append((path, pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]))
+        rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]))
     if save_dir:
         import os
         os.makedirs(save_dir, exist_ok=True)
         with open(os.path.join(save_dir, "pred_results.csv"), "w") as f:
-            f.write(",PATH,RMSE,PSNR,SSIM\n")
+            f.write(",PATH,PL,TML,RMSE,PSNR,SSIM\n" if vgg is not None else ",PATH,RMSE,PSNR,SSIM\n")
             for i, r in enumerate(rows):
-                f.write(f"{i},{r[0]},{r[1]},{r[2]},{r[3]}\n")
+                f.write(f"{i}," + ",".join(str(v) for v in r) + "\n")
     return {k: round(mm.global_avg, 7) for k, mm in meters.items()}

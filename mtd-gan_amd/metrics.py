@@ -1,6 +1,13 @@
-"""Pixel metrics of the reference's evaluation loops -- mirror of metrics.py:172-244 (compute_RMSE / compute_PSNR /
-compute_SSIM: same arguments, same (input, gt, pred) float triples) on the HIP kernel `mtd_image_metrics`.
-The perceptual / feature metrics (PL, TML, FID: VGG16 / InceptionV3 from torchvision weights) are out of scope."""
+"""Metrics of the reference's evaluation loops -- mirror of metrics.py:43-244.
+
+Pixel metrics (metrics.py:172-244: compute_RMSE / compute_PSNR / compute_SSIM, same arguments, same (input, gt, pred) float
+triples) on the HIP kernel `mtd_image_metrics`.
+
+Perceptual metrics (metrics.py:43-168: compute_PL / compute_TML on the five VGG-19 feature maps relu1_1 ... relu5_1, same
+arguments plus the keyword `vgg`): the feature stack is `VGG19Features`, built from a torchvision `vgg19` state dict that the
+caller hands over (no pretrained weights ship with this package), its convolutions are `kernels.conv` launches, the pools
+`mtd_maxpool2x2`, the L1 means `kernels.loss_terms` and the per-patch Gram-matrix distance `mtd_patch_gram_l1`.
+Inference only: no gradient flows through them.  FID (InceptionV3 features and a matrix square root) is out of scope."""
 import numpy as np
 import torch
 
@@ -68,3 +75,201 @@ def pixel_metrics(input, target, pred):
         out["psnr"].append(_psnr(sse, n, 1.0))
         out["ssim"].append(float(np.float32(ssum / n)))
     return {k: tuple(v) for k, v in out.items()}
+
+
+# ================================================================================================ perceptual metrics
+# torchvision vgg19().features: index of each conv -> (C_in, C_out); ReLU follows at index + 1
+_VGG19_CONVS = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256), (16, 256, 256),
+                (19, 256, 512), (21, 512, 512), (23, 512, 512), (25, 512, 512), (28, 512, 512))
+_VGG19_POOL_AFTER = (3, 8, 17, 26)          # nn.MaxPool2d(2, 2) at indices 4, 9, 18, 27
+_VGG19_TAPS = (1, 6, 11, 20, 29)            # relu1_1, relu2_1, relu3_1, relu4_1, relu5_1 (metrics.py:53-62)
+LEVEL_WEIGHTS = (1.0 / 32, 1.0 / 16, 1.0 / 8, 1.0 / 4, 1.0)      # metrics.py:82,118
+TML_PATCH = 16                              # TextureMatchingLoss(patch_size=16, use_patch=True), the reference's default
+_MAX_MAP_BYTES = (1 << 31) - 1              # the conv entry points address a map with 32-bit byte offsets: strictly below 2^31 bytes
+
+
+def maxpool2x2(x):
+    """nn.MaxPool2d(2, 2) of a contiguous NHWC fp32 map (mtd_maxpool2x2)."""
+    B, H, W, Cc = x.shape
+    out = torch.empty((B, H // 2, W // 2, Cc), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().mtd_maxpool2x2(x.data_ptr(), out.data_ptr(), B, H, W, Cc, K.stream_ptr()), "mtd_maxpool2x2")
+    return out
+
+
+def patch_gram_l1(x, y, out=None):
+    """Sum over the 16 x 16 patches and all C^2 entries of |G(x) - G(y)| of two contiguous NHWC fp32 maps: one device double
+    (mtd_patch_gram_l1; written to the 1-element float64 tensor `out` when given)."""
+    if x.shape != y.shape or x.dim() != 4 or not (x.is_cuda and y.is_cuda) or not (x.is_contiguous() and y.is_contiguous()):
+        raise ValueError("patch_gram_l1: two contiguous CUDA NHWC maps of one shape expected")
+    B, h, w, Cc = x.shape
+    L = _lib.lib()
+    need = L.mtd_patch_gram_l1_ws_bytes(B, h, w, Cc)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=x.device)
+    ws = K.workspace(max(need, 8), x.device)
+    _lib.check(L.mtd_patch_gram_l1(x.data_ptr(), y.data_ptr(), B, h, w, Cc, out.data_ptr(), ws.data_ptr(), K.stream_ptr()), "mtd_patch_gram_l1")
+    return out
+
+
+class VGG19Features:
+    """The feature part of torchvision's VGG-19 up to relu5_1 on the HIP conv kernels, for single-channel images.
+
+    `weights`: a state dict in torchvision's `vgg19` key layout (features.{0,2,5,...,28}.{weight,bias}; other keys such as
+    classifier.* are ignored) or a path to one (read with torch.load(..., weights_only=True)).  The reference feeds
+    x.repeat(1, 3, 1, 1) without ImageNet normalisation (metrics.py:87,145), so the first layer is folded to 1 -> 64 channels:
+    its three input-channel slices are summed once, here.  The weights go to the device of the first call's input, once."""
+
+    def __init__(self, weights):
+        if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
+            weights = torch.load(weights, map_location="cpu", weights_only=True)
+        self.layers = []                     # (features index, weight (N, C, 3, 3), bias (N,)) in fp32, first layer folded
+        for idx, cin, cout in _VGG19_CONVS:
+            got = []
+            for leaf, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
+                key = f"features.{idx}.{leaf}"
+                if key not in weights:
+                    raise ValueError(f"VGG19Features: the state dict has no {key!r}")
+                t = weights[key]
+                if not torch.is_tensor(t) or tuple(t.shape) != shape:
+                    raise ValueError(f"VGG19Features: {key!r} has shape {tuple(getattr(t, 'shape', ()))}, expected {shape}")
+                got.append(t.detach())
+            w, b = got
+            if idx == 0:
+                w = w.double().sum(dim=1, keepdim=True)
+            self.layers.append((idx, w.float().contiguous(), b.float().contiguous()))
+        self._device = None
+
+    def to(self, device):
+        device = torch.device(device)
+        if self._device != device:
+            self.layers = [(i, w.to(device), b.to(device)) for i, w, b in self.layers]
+            self._device = device
+        return self
+
+    def _chunk(self, x):
+        """The five maps of one chunk of images, (B, H, W, 1) in NHWC."""
+        maps = []
+        t = x
+        for idx, w, b in self.layers:
+            B, H, W, Cc = t.shape
+            N = w.shape[0]
+            out = torch.empty((B, H, W, N), dtype=torch.float32, device=t.device)
+            K.conv(t, w, K.geom_fwd(B, H, W, 3, 1, 1), N, Cc, Cc * 9, 9, out, bias=b, act=_lib.ACT_RELU)
+            t = out
+            if idx + 1 in _VGG19_TAPS:
+                maps.append(t)
+            if idx + 1 in _VGG19_POOL_AFTER:
+                t = maxpool2x2(t)
+        return maps
+
+    @torch.no_grad()
+    def __call__(self, x):
+        """x: (B, 1, H, W) fp32 CUDA, H, W >= 16.  Returns the NHWC maps relu1_1 ... relu5_1:
+        (B, H, W, 64), (B, H/2, W/2, 128), (B, H/4, W/4, 256), (B, H/8, W/8, 512), (B, H/16, W/16, 512) (floor at every pool)."""
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise AssertionError("VGG19Features expects a (B,1,H,W) tensor")
+        if not x.is_cuda:
+            raise RuntimeError("VGG19Features: HIP path needs CUDA tensors (no CPU fallback)")
+        B, _, H, W = x.shape
+        if H < 16 or W < 16:
+            raise ValueError(f"VGG19Features: images of at least 16 x 16 expected (four pools before relu5_1), got {H} x {W}")
+        per_image = H * W * 64 * 4                   # relu1_1, the largest map
+        if per_image > _MAX_MAP_BYTES:
+            raise ValueError(f"VGG19Features: a {H} x {W} image gives a first feature map of 2^31 bytes or more")
+        self.to(x.device)
+        x = x.detach().contiguous().float().reshape(B, H, W, 1)       # one channel: NCHW and NHWC coincide
+        step = max(1, _MAX_MAP_BYTES // per_image)
+        if B <= step:
+            return self._chunk(x)
+        parts = [self._chunk(x[i:i + step]) for i in range(0, B, step)]
+        return [torch.cat([p[lvl] for p in parts]) for lvl in range(5)]
+
+
+def _perceptual_inputs(name, input, target, pred, vgg, min_side):
+    if not isinstance(vgg, VGG19Features):
+        raise TypeError(f"{name}: pass the feature network as vgg=VGG19Features(state_dict) (no pretrained weights ship with this package)")
+    for t in (input, target, pred):
+        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
+            raise AssertionError(f"{name} expects three (B,1,H,W) tensors of the same shape")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: HIP path needs CUDA tensors (no CPU fallback)")
+    H, W = target.shape[2:]
+    if H < min_side or W < min_side:
+        raise ValueError(f"{name}: images of at least {min_side} x {min_side} expected, got {H} x {W}"
+                         + (" (relu5_1 must hold one 16 x 16 patch; the reference returns NaN here)" if min_side > 16 else ""))
+
+
+def _stacked_features(vgg, target, others):
+    """The network once on the stacked images: per level (target map, [map of each other])."""
+    B = target.shape[0]
+    maps = vgg(torch.cat([target] + list(others)))
+    return [(m[:B], [m[(k + 1) * B:(k + 2) * B] for k in range(len(others))]) for m in maps]
+
+
+def _pl_values(levels, who):
+    """who: indices into (target, *others) with 0 = the target itself, whose distance to itself is the constant 0 (no launch).
+    One float per entry of `who`."""
+    terms = []
+    for k in who:
+        if k == 0:
+            continue
+        for wgt, (ft, fo) in zip(LEVEL_WEIGHTS, levels):
+            terms.append(K.make_term(1, fo[k - 1], ft, scale=wgt / ft.numel()))
+    dev = levels[0][0].device
+    vals = K.loss_terms(terms, dev)
+    others = [k for k in who if k != 0]
+    sums = K.scalar_sums([(vals[5 * i:5 * i + 5], None) for i in range(len(others))], dev)
+    if len(others) == len(who):
+        return sums
+    zero = torch.zeros(1, dtype=torch.float32, device=dev)
+    return torch.cat([zero if k == 0 else sums[others.index(k):others.index(k) + 1] for k in who])      # (layout only)
+
+
+def _tml_values(levels, who):
+    """As _pl_values: the target's own entry costs no Gram launch, its five sums stay 0."""
+    import ctypes
+    dev = levels[0][0].device
+    sums = torch.zeros(5 * len(who), dtype=torch.float64, device=dev)
+    scales = (ctypes.c_double * 5)()
+    for lvl, (wgt, (ft, fo)) in enumerate(zip(LEVEL_WEIGHTS, levels)):
+        B, h, w, Cc = ft.shape
+        scales[lvl] = wgt / (float(B * (h // TML_PATCH) * (w // TML_PATCH)) * Cc * Cc)
+        for i, k in enumerate(who):
+            if k != 0:
+                patch_gram_l1(fo[k - 1], ft, out=sums[5 * i + lvl:5 * i + lvl + 1])
+    out = torch.empty(len(who), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().mtd_scaled_sums_f64(sums.data_ptr(), len(who), 5, scales, out.data_ptr(), K.stream_ptr()), "mtd_scaled_sums_f64")
+    return out
+
+
+def _triple(vals, option):
+    return (vals[0], vals[1], vals[2]) if option else vals[0]
+
+
+@torch.no_grad()
+def compute_PL(input, target, pred, option=True, device=None, *, vgg):
+    """metrics.py:93-106: sum_i w_i * mean|f_i(a) - f_i(target)| over the five VGG-19 maps, w = [1/32, 1/16, 1/8, 1/4, 1], for
+    a = input, target, pred (option=True: a triple of 0-dim device tensors, the middle one the constant 0) or pred alone.
+    `device` is accepted for the reference's signature; the tensors' device is used.  H, W >= 16."""
+    _perceptual_inputs("compute_PL", input, target, pred, vgg, 16)
+    levels = _stacked_features(vgg, target, (input, pred) if option else (pred,))
+    return _triple(_pl_values(levels, (1, 0, 2) if option else (1,)), option)
+
+
+@torch.no_grad()
+def compute_TML(input, target, pred, option=True, device=None, *, vgg):
+    """metrics.py:156-168 with its defaults (patch 16, use_patch=True): sum_i w_i * mean over (B * patches, C, C) of
+    |G(f_i(a)) - G(f_i(target))|, G the unnormalised Gram matrix of a 16 x 16 patch of the map.  H, W >= 256, so that relu5_1
+    holds a patch (the reference's nn.Unfold yields no patch below that and its mean is NaN): ValueError otherwise."""
+    _perceptual_inputs("compute_TML", input, target, pred, vgg, 16 * TML_PATCH)
+    levels = _stacked_features(vgg, target, (input, pred) if option else (pred,))
+    return _triple(_tml_values(levels, (1, 0, 2) if option else (1,)), option)
+
+
+@torch.no_grad()
+def perceptual_metrics(input, target, pred, vgg):
+    """PL and TML of the test loop from ONE pass of the network: a device vector (input_pl, gt_pl, pred_pl, input_tml, gt_tml,
+    pred_tml), the same values as compute_PL / compute_TML."""
+    _perceptual_inputs("perceptual_metrics", input, target, pred, vgg, 16 * TML_PATCH)
+    levels = _stacked_features(vgg, target, (input, pred))
+    return torch.cat([_pl_values(levels, (1, 0, 2)), _tml_values(levels, (1, 0, 2))])
