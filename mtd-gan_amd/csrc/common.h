@@ -4,17 +4,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include "../../include/mtdgan_hip.h"
+#include "host_util.h"      // mtd_lab_env (the lab switches), aligned16, geom_pixels
 
-// Lab switches.  The kernel-selection / tuning environment variables of rounds 1-4 (MTD_WINO_*, MTD_WGRAD_*, MTD_IGEMM_*, ...)
-// exist only in a library built with -DMTD_LAB (tools/ probes: `MTD_LAB_BUILD=1 python mtd-gan_amd/_build.py --force`).  The
-// shipped library reads NO environment variable: a stray MTD_* in a user's shell cannot change which kernel runs.  The few
-// options that are meant to be flipped at run time go through mtd_set_option() (api.hip), each exercised by a test.
-#include <stdlib.h>
-#ifdef MTD_LAB
-static inline const char* mtd_lab_env(const char* name) { return getenv(name); }
-#else
-static inline const char* mtd_lab_env(const char*) { return nullptr; }
-#endif
 // run-time options (api.hip: mtd_set_option / mtd_get_option)
 enum { MTD_OPT_C32F_SAFE_WAIT = 0, MTD_OPT_WINO_SPLIT, MTD_OPT_COUNT };
 int mtd_option(int id);
@@ -85,8 +76,6 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     return v;
 }
 
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-static inline long long geom_pixels(const mtd_geom& g) { return (long long)g.B * g.OH * g.OW; }
 // accumulator scale of a conv launch: one value, or two for the two batch halves of a paired discriminator pass
 struct ScalePair { float s0, s1; int split; };
 __device__ __forceinline__ ScalePair load_scale(const mtd_conv_args& a) {

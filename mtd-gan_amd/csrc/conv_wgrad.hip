@@ -13,6 +13,7 @@
 //
 // Roofline: fp32 MFMA.  Algorithmic flops = 2*M*N*C*taps.
 #include "common.h"
+#include "conv_wgrad_plan.h"
 #include "fft64.h"
 
 namespace {
@@ -1131,435 +1132,207 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_multi_kernel(const mtd_wgra
 #include "conv_wgrad_wino_s2.h"
 #include "conv_wgrad_wino32.h"
 
-struct WPlan { int cfg, WN, WC, TG, ppw, nsplit, ntg, nw; };
-
-int g_wforce_cfg = -1, g_wforce_split = -1;     // tuning hook (mtd_conv_wgrad_override)
-int g_wforce_nw = 0;                            // waves per workgroup of the register-operand kernels (env MTD_WGRAD_NW, lab only)
-constexpr int NWCFG = 7;
-const int kWcfgWN[NWCFG] = {1, 1, 2, 1, 1, 1, 2};
-const int kWcfgWC[NWCFG] = {1, 1, 2, 1, 1, 1, 2};
-const int kWcfgTG[NWCFG] = {9, 4, 1, 8, 3, 1, 3};
-// (cfg 13: wgrad_taps_kernel.  A 64 x 64 tile with a whole filter row per workgroup, wgrad_kernel<2, 2, 4>, needs 256
-// accumulator registers and spilled 600 bytes per lane: not instantiated.)
-
-// row-window kernel: stride 1, rows of a multiple of 16 output pixels, 3x3 (unit tap spacing) or 1x1
-bool row_window_ok(const mtd_wgrad_args& a) {
-    const mtd_geom& g = a.g;
-    if (g.in_sy != 1 || g.in_sx != 1 || (g.OW % 16) != 0) return false;
-    if (g.TH == 1 && g.TW == 1) return true;
-    return g.TH == 3 && g.TW == 3 && (g.tap_dx == 1 || g.tap_dx == -1);
-}
-
-// block-window kernel: 3x3 / stride 1 / pad 1 on square 8x8, 4x4 or 2x2 maps (forward tap order)
-int block_window_w(const mtd_wgrad_args& a) {
-    const mtd_geom& g = a.g;
-    if (g.in_sy != 1 || g.in_sx != 1 || g.TH != 3 || g.TW != 3 || g.tap_dy != 1 || g.tap_dx != 1) return 0;
-    if (g.off_y != -1 || g.off_x != -1 || g.IH != g.OH || g.IW != g.OW || g.OH != g.OW) return 0;
-    return (g.OW == 8 || g.OW == 4 || g.OW == 2) ? g.OW : 0;
-}
-
-// g_wplan_div: 2 while planning ONE of the two problems of a pair launch (half the workgroup targets); a parameter, not a
-// global, so that concurrent callers (main thread + autograd's backward thread, several devices) cannot see each other's value
-WPlan make_wplan(const mtd_wgrad_args& a, const int g_wplan_div = 1) {
-    WPlan pl{};
-    const int T = a.g.TH * a.g.TW;
-    const long long M = geom_pixels(a.g);
-    // LDS-staged kernels (strided convs and feature maps narrower than 16 pixels); choices from tools/census.py --sweep-wgrad
-    if (T == 1 && a.N % 64 == 0 && a.C % 64 == 0) pl.cfg = 2;
-    else if (T <= 4) pl.cfg = 1;
-    else if (T <= 9) pl.cfg = (M <= 2048) ? 4 : 0;              // few pixels, many tiles: 3 taps per wave, no pixel split
-    else {
-        // 4x4 taps (round 6, tools/wgrad_s2_small_probe.py: both halves of a paired pass are one launch now, so down4 has 1024 pixels
-        // and down5 256): 64 x 64 tiles with one tap each from 1024 pixels on (108 us against 140 for 32 x 32 tiles x 3 taps), 32 x 32
-        // tiles with one tap each up to 256 pixels (42 us against 51)
-        static const int env_t16 = [] { const char* e = mtd_lab_env("MTD_WGRAD_T16_PLAN"); return e ? atoi(e) : 1; }();      // (0: round 5's thresholds)
-        if (!env_t16) pl.cfg = (M >= 2048 && a.N % 64 == 0 && a.C % 64 == 0) ? 2 : 4;
-        else if (M >= 1024 && a.N % 64 == 0 && a.C % 64 == 0) pl.cfg = 2;
-        else pl.cfg = (M <= 256) ? 5 : 4;
-    }
-    // Winograd F(2x2, 3x3) on ONE 32 x 32 block (conv_wgrad_wino32.h): the generator's 32 -> 32 layers on maps of at least
-    // MTD_WGRAD_WINO32_MIN_HW pixels a side (where the row-window kernel is the plan otherwise).  cfg 19; ppw = chunks of 16 tiles per slice.
-    static const int env_w32 = [] { const char* e = mtd_lab_env("MTD_WGRAD_WINO32"); return e ? atoi(e) : 1; }();
-    static const int env_w32_hw = [] { const char* e = mtd_lab_env("MTD_WGRAD_WINO32_MIN_HW"); return e ? atoi(e) : 32; }();
-    if (((env_w32 && g_wforce_cfg == -1) || g_wforce_cfg == 19) && wgrad_wino32_ok(a) && a.g.OH >= env_w32_hw && a.g.OW >= env_w32_hw) {
-        const long long tiles = (long long)a.g.B * (a.g.OH / 2) * (a.g.OW / 2);
-        const long long chunks = (tiles + W32_T - 1) / W32_T;
-        long long ns = 256 / g_wplan_div;
-        if (g_wforce_split > 0) ns = g_wforce_split;
-        if (ns > chunks / 4) ns = chunks / 4;
-        if (ns > chunks) ns = chunks;
-        if (ns >= 2) {
-            const long long cps = (chunks + ns - 1) / ns;
-            ns = (chunks + cps - 1) / cps;
-            if (ns >= 2) {
-                pl.cfg = 19;
-                pl.WN = 1; pl.WC = 1; pl.TG = T; pl.ntg = 1; pl.nw = 8;
-                pl.ppw = (int)cps;
-                pl.nsplit = (int)ns;
-                return pl;
-            }
-        }
-    }
-    // Winograd F(3x3, 2x2) form of the 4x4 / stride-2 layers (conv_wgrad_wino_s2.h): output maps of at least MTD_WGRAD_WINO_S2_MIN_HW
-    // pixels a side.  cfg 18; planned like cfg 16 (ppw = chunks of eight tiles per pixel split, always through slabs).
-    static const int env_ws2 = [] { const char* e = mtd_lab_env("MTD_WGRAD_WINO_S2"); return e ? atoi(e) : 1; }();
-    static const int env_ws2_hw = [] { const char* e = mtd_lab_env("MTD_WGRAD_WINO_S2_MIN_HW"); return e ? atoi(e) : 8; }();
-    if (((env_ws2 && g_wforce_cfg == -1) || g_wforce_cfg == 18) && wgrad_wino_s2_ok(a) && a.g.OH >= env_ws2_hw && a.g.OW >= env_ws2_hw) {
-        pl.cfg = 18;
-        pl.WN = 2; pl.WC = 2; pl.TG = T; pl.ntg = 1; pl.nw = 8;
-        const long long blocks = wgrad_wino_s2_blocks(a);
-        const long long chunks = (wgrad_wino_s2_tiles(a, a.g.B) + WGW_T - 1) / WGW_T;
-        long long ns = (256 + blocks - 1) / blocks;
-        if (g_wforce_split > 0) ns = g_wforce_split;
-        if (ns > chunks / 4) ns = chunks / 4;
-        if (ns < 2) ns = 2;
-        if (ns > chunks) ns = chunks;
-        const long long cps = (chunks + ns - 1) / ns;
-        ns = (chunks + cps - 1) / cps;
-        if (ns >= 2) {
-            pl.ppw = (int)cps;
-            pl.nsplit = (int)ns;
-            return pl;
-        }
-        pl = WPlan{};
-        pl.cfg = (M >= 1024 && a.N % 64 == 0 && a.C % 64 == 0) ? 2 : ((M <= 256) ? 5 : 4);
-    }
-    static const int env_s2 = [] { const char* e = mtd_lab_env("MTD_WGRAD_S2"); return e ? atoi(e) : 1; }();
-    if (a.g.TH == 4 && a.g.TW == 4 && a.g.in_sy == 2 && a.g.in_sx == 2 && a.g.off_y == -1 && a.g.off_x == -1 && a.g.tap_dy == 1 &&
-        a.g.tap_dx == 1 && (a.g.OH % 8) == 0 && (a.g.OW % 8) == 0 && ((env_s2 && g_wforce_cfg == -1) || g_wforce_cfg == 15)) {
-        // halo-window kernel: 8 x 8 pixel blocks; ~512 workgroups of the single-buffer form, two per CU (51 KB of LDS each), which take
-        // turns on the matrix cores: 46.6-49.6 us per layer against 51-54 for 256 double-buffered workgroups and 57 for wgrad_kernel<2,2,1>
-        pl.cfg = 15;
-        pl.WN = 1; pl.WC = 1; pl.TG = T; pl.ntg = 1; pl.nw = 4;
-        const long long tiles = (long long)(a.N / 32) * (a.C / 32);
-        const long long NB = (long long)a.g.B * (a.g.OH / 8) * (a.g.OW / 8);
-        static const int env_s2wgs = [] { const char* e = mtd_lab_env("MTD_WGRAD_S2_WGS"); return e ? atoi(e) : 512; }();
-        long long ns = (env_s2wgs / g_wplan_div + tiles - 1) / tiles;
-        if (g_wforce_split > 0) ns = g_wforce_split;
-        if (ns > NB) ns = NB;
-        if (ns < 1) ns = 1;
-        const long long bpw = (NB + ns - 1) / ns;
-        ns = (NB + bpw - 1) / bpw;
-        pl.ppw = (int)bpw;
-        pl.nsplit = (int)ns;
-        return pl;
-    }
-    static const int env_taps = [] { const char* e = mtd_lab_env("MTD_WGRAD_TAPS"); return e ? atoi(e) : 1; }();
-    static const int env_taps_maxm = [] { const char* e = mtd_lab_env("MTD_WGRAD_TAPS_MAXM"); return e ? atoi(e) : 128; }();
-    if (a.g.TH == 4 && a.g.TW == 4 && ((env_taps && g_wforce_cfg == -1 && M <= env_taps_maxm) || g_wforce_cfg == 13)) {
-        // all-taps kernel: ~one workgroup per CU; pixels per workgroup a multiple of 32
-        pl.cfg = 13;
-        pl.WN = 1; pl.WC = 1; pl.TG = T; pl.ntg = 1; pl.nw = 4;
-        const long long tiles = (long long)(a.N / 32) * (a.C / 32);
-        static const int env_wgs = [] { const char* e = mtd_lab_env("MTD_WGRAD_TAPS_WGS"); return e ? atoi(e) : 256; }();
-        long long ns = (env_wgs / g_wplan_div + tiles - 1) / tiles;
-        if (g_wforce_split > 0) ns = g_wforce_split;
-        const long long max_splits = (M + 31) / 32;
-        if (ns > max_splits) ns = max_splits;
-        if (ns < 1) ns = 1;
-        long long ppw = (M + ns - 1) / ns;
-        ppw = ((ppw + 31) / 32) * 32;
-        ns = (M + ppw - 1) / ppw;
-        pl.ppw = (int)ppw;
-        pl.nsplit = (int)ns;
-        return pl;
-    }
-    // Winograd F(2x2, 3x3) form (conv_wgrad_wino.h): 3x3 stride-1 layers with N, C multiples of 64 on maps of at least
-    // MTD_WGRAD_WINO_MIN_HW pixels a side.  cfg 16; ppw = chunks of eight tiles per pixel split.
-    static const int env_wino = [] { const char* e = mtd_lab_env("MTD_WGRAD_WINO"); return e ? atoi(e) : 1; }();
-    static const int env_wino_hw = [] { const char* e = mtd_lab_env("MTD_WGRAD_WINO_MIN_HW"); return e ? atoi(e) : 8; }();
-    if (((env_wino && g_wforce_cfg == -1) || g_wforce_cfg == 16) && wgrad_wino_ok(a) && a.g.OH >= env_wino_hw && a.g.OW >= env_wino_hw) {
-        pl.cfg = 16;
-        pl.WN = 2; pl.WC = 2; pl.TG = T; pl.ntg = 1; pl.nw = 8;
-        const long long blocks = wgrad_wino_blocks(a);            // 64 x 64 (F(2x2)) or 64 x 32 (F(2x4)) blocks of (n, c)
-        const long long chunks = (wgrad_wino_tiles(a, a.g.B) + WGW_T - 1) / WGW_T;
-        long long ns = (256 + blocks - 1) / blocks;              // about one workgroup per CU
-        if (g_wforce_split > 0) ns = g_wforce_split;
-        if (ns > chunks / 4) ns = chunks / 4;                    // at least four chunks per slice
-        if (ns < 2) ns = 2;                                      // (always through slabs: the kernel has no direct-store form)
-        if (ns > chunks) ns = chunks;
-        const long long cps = (chunks + ns - 1) / ns;
-        ns = (chunks + cps - 1) / cps;
-        if (ns >= 2) {
-            pl.ppw = (int)cps;
-            pl.nsplit = (int)ns;
-            return pl;
-        }
-        pl = WPlan{};
-        pl.cfg = (M <= 2048) ? 4 : 0;
-    }
-    const int bw = block_window_w(a);
-    if ((row_window_ok(a) || bw) && g_wforce_cfg != -2) {   // override cfg -2: keep the LDS-staged kernels (A/B comparison)
-        pl.cfg = bw ? (bw == 8 ? 10 : (bw == 4 ? 11 : 12)) : ((T == 1) ? 9 : (a.g.tap_dx > 0 ? 7 : 8));
-        pl.WN = 1; pl.WC = 1; pl.TG = T; pl.ntg = 1;
-        long long tiles = (long long)(a.N / 32) * (a.C / 32);
-        long long want_splits = (256 / g_wplan_div + tiles - 1) / tiles;      // sweep: ~one workgroup per CU, longer pixel runs per wave
-        if (g_wforce_split > 0) want_splits = g_wforce_split;
-        long long max_splits = (M + 127) / 128;
-        long long ns = want_splits < 1 ? 1 : want_splits;
-        if (ns > max_splits) ns = max_splits;
-        // four waves per workgroup; eight (two per SIMD, same workgroup count and slab traffic) measured 1 % faster
-        // standalone and no different inside the step, so it stays a lab switch (MTD_WGRAD_NW=8)
-        pl.nw = (g_wforce_nw == 8 && bw != 8) ? 8 : 4;    // (the 8x8 window kernel needs more than 256 registers)
-        long long ppw = (M + ns * pl.nw - 1) / (ns * pl.nw);
-        ppw = ((ppw + 31) / 32) * 32;
-        ns = (M + ppw * pl.nw - 1) / (ppw * pl.nw);
-        pl.ppw = (int)ppw;
-        pl.nsplit = (int)ns;
-        return pl;
-    }
-    if (g_wforce_cfg >= 0 && g_wforce_cfg < NWCFG && a.N % (32 * kWcfgWN[g_wforce_cfg]) == 0 && a.C % (32 * kWcfgWC[g_wforce_cfg]) == 0)
-        pl.cfg = g_wforce_cfg;
-    pl.WN = kWcfgWN[pl.cfg];
-    pl.WC = kWcfgWC[pl.cfg];
-    pl.TG = kWcfgTG[pl.cfg];
-    pl.ntg = (T + pl.TG - 1) / pl.TG;
-    pl.nw = 4;
-    long long tiles = (long long)(a.N / (32 * pl.WN)) * (a.C / (32 * pl.WC)) * pl.ntg;
-    // aim for >= 512 workgroups; every wave gets a multiple of 32 pixels
-    long long want_splits = (512 / g_wplan_div + tiles - 1) / tiles;
-    if (g_wforce_split > 0) want_splits = g_wforce_split;
-    long long max_splits = (M + 127) / 128;             // at least 32 px per wave
-    long long ns = want_splits < 1 ? 1 : want_splits;
-    if (ns > max_splits) ns = max_splits;
-    long long ppw = (M + ns * 4 - 1) / (ns * 4);
-    ppw = ((ppw + 31) / 32) * 32;
-    ns = (M + ppw * 4 - 1) / (ppw * 4);
-    pl.ppw = (int)ppw;
-    pl.nsplit = (int)ns;
-    return pl;
-}
-
-bool is_direct(const mtd_wgrad_args& a) { return (a.N % 32) || (a.C % 32); }
-
-int check_wargs(const mtd_wgrad_args& a) {
-    if (!a.p || !a.q || !a.dw) return MTD_EINVAL;
-    if (a.N <= 0 || a.C <= 0) return MTD_EINVAL;
-    if (is_direct(a)) {
-        if (a.N != 1 && a.C != 1) return MTD_EINVAL;
-        const mtd_geom& g = a.g;
-        if (g.B <= 0 || g.TH <= 0 || g.TW <= 0 || g.TH * g.TW > 16) return MTD_EINVAL;
-        if (a.p_ld < a.N || a.q_ld < a.C) return MTD_EINVAL;
-        return MTD_OK;
-    }
-    const mtd_geom& g = a.g;
-    if (g.B <= 0 || g.IH <= 0 || g.IW <= 0 || g.OH <= 0 || g.OW <= 0) return MTD_EINVAL;
-    if (g.TH <= 0 || g.TW <= 0 || g.TH * g.TW > 16) return MTD_EINVAL;
-    if (geom_pixels(g) > (1ll << 30)) return MTD_EINVAL;
-    if (a.p_ld < a.N || a.q_ld < a.C || (a.p_ld % 4) || (a.q_ld % 4)) return MTD_EINVAL;
-    if (!aligned16(a.p) || !aligned16(a.q)) return MTD_EALIGN;
-    if (a.half_scale && (!a.half_scale2 || a.m_first <= 0 || (a.m_first % 32) || a.m_first >= geom_pixels(g))) return MTD_EINVAL;
-    return MTD_OK;
-}
-
-constexpr int GS = 64;   // slabs summed per reduce stage (eight loads in flight per thread: 64 slabs cost less than a second launch)
-
-size_t wgrad_ws_floats(const mtd_wgrad_args& a, int nsplit) {
-    const long long T = a.g.TH * a.g.TW;
-    const long long stride = T * a.N * a.C + a.N;
-    long long total = (long long)nsplit * stride;
-    long long ns = nsplit;
-    while (ns > GS) {           // intermediate stages
-        ns = (ns + GS - 1) / GS;
-        total += ns * stride;
-    }
-    return (size_t)total;
-}
-
 }  // namespace
+
+// (the planner -- plans, domains, pixel split, workspace -- is conv_wgrad_plan.h)
 
 #ifndef MTD_NO_API      // (conv_c32_bwd.hip includes this file for its kernels and helpers only)
 int mtd_direct_wgrad_launch(const mtd_wgrad_args* a, int* nslab_out, long long slab_stride, void* stream);
 int mtd_direct_wgrad_nslab(const mtd_wgrad_args* a);
 
-extern "C" int mtd_conv_wgrad_override(int cfg, int nsplit) {
-    g_wforce_cfg = cfg;
-    g_wforce_split = nsplit;
+// p for a launch over a's operands with nslab slabs; MTD_EINVAL where an operand is beyond the 32-bit buffer range.  (ppw and nCt
+// are the plan's: the caller's.  The tap displacements are read by wgrad_kernel<> only.)
+static int fill_wgrad_params(WgradParams& p, const mtd_wgrad_args& a, int nslab) {
+    const mtd_geom& g = a.g;
+    p.a = a;
+    p.M = (int)geom_pixels(g);
+    p.T = g.TH * g.TW;
+    p.nslab = nslab;
+    p.slab_stride = (long long)p.T * a.N * a.C + a.N;
+    for (int t = 0; t < p.T; ++t) {
+        const int ty = t / g.TW, tx = t % g.TW;
+        p.tap_dy[t] = ty * g.tap_dy;
+        p.tap_dx[t] = tx * g.tap_dx;
+        p.tap_delta[t] = (int)((((long long)(ty * g.tap_dy) * g.IW + tx * g.tap_dx) * a.q_ld) * 4);
+    }
+    const long long pb = (((long long)p.M - 1) * a.p_ld + a.N) * 4;
+    const long long qb = (((long long)g.B * g.IH * g.IW - 1) * a.q_ld + a.C) * 4;
+    if (pb >= (1ll << 31) || qb >= (1ll << 31)) return MTD_EINVAL;
+    p.p_bytes = (unsigned)pb;
+    p.q_bytes = (unsigned)qb;
     return MTD_OK;
+}
+
+// the pair form of the Winograd kernels: slabs [0, ns_first) sum images [0, b_first), the others the rest (ns_first = 0: one range);
+// p_add: the second cotangent of mtd_conv_wgrad_pair_sum or null
+struct WinoRanges { int ns_first = 0, b_first = 0; const float* p_add = nullptr; };
+
+static void fill_wino_params(WgradWinoParams& wp, const WgradParams& p, const WPlan& pl, const WinoRanges& r) {
+    const mtd_geom& g = p.a.g;
+    const bool s2 = pl.cfg == WCFG_WINO_S2;          // 3 x 3 output tiles (ragged ones in full); 2 x 2 otherwise
+    wp.w = p;
+    wp.tiles_x = s2 ? (g.OW + 2) / 3 : g.OW / 2;
+    wp.tiles_per_image = (s2 ? (g.OH + 2) / 3 : g.OH / 2) * wp.tiles_x;
+    wp.ntiles = g.B * wp.tiles_per_image;
+    wp.chunks_per_split = pl.ppw;
+    wp.ns_first = r.ns_first;
+    wp.first_tiles = r.b_first * wp.tiles_per_image;
+    wp.p_add = r.p_add;
+}
+
+// the 3x3 row-window kernel in tap order DX.  64 KB of dynamic LDS nobody uses caps it at ONE workgroup (one wave per SIMD) per CU.
+// Alone in a stream that changes nothing (generator step: 31.7 us per launch either way); in the full step, where it runs on a
+// side stream beside the data-gradient chain, a second workgroup on a CU took the slots of the other stream's
+// kernel: 44.47 -> 44.03 ms per step (three A/B runs each, tools/wgrad_pad_full.sh).  MTD_WGRAD_LDS_PAD=0 is the old launch.
+// One (n, c) tile and `rows`: the forward row transform rides in the same launch.
+#define WGRAD_LAUNCH_ROW3(DX)                                                                                        \
+    do {                                                                                                             \
+        if (pl.nw == 8) MTD_LAUNCH((wgrad_row_kernel<3, 3, DX, 8>), grid, dim3(512), 0, s, p);                      \
+        else if (rows && grid.y == 1 && grid.z == 1) {                                                               \
+            const dim3 fg(grid.x + (unsigned)((rows->npairs + 7) / 8));                                              \
+            MTD_LAUNCH((wgrad_row_rfft_kernel<DX>), fg, dim3(256), 0, s, p, (int)grid.x, *rows);                     \
+            *rows_done = true;                                                                                       \
+        } else MTD_LAUNCH((wgrad_row_kernel<3, 3, DX, 4>), grid, dim3(256), (unsigned)wgrad_lab().lds_pad, s, p);   \
+    } while (0)
+
+// The plan's slab-producing kernel over p (p.ppw = pl.ppw, p.nCt = c tiles).  np: problems of p.a's shape in the launch (2: the
+// pair form of WgradParams::pair_ns); r: the Winograd kernels' pair form.  rows != nullptr: also run the forward row transform
+// `rows` describes, inside the same launch if the plan is the 3x3 row-window kernel on one (n, c) tile -- *rows_done says whether it was.
+static int wgrad_launch(const WPlan& pl, const WgradParams& p, hipStream_t s, int np = 1, const WinoRanges& r = WinoRanges{},
+                        const RowsArgs* rows = nullptr, bool* rows_done = nullptr) {
+    const mtd_wgrad_args& a = p.a;
+    const mtd_geom& g = a.g;
+    if (pl.cfg < 0 || pl.cfg >= WCFG_COUNT || !kWgradCfg[pl.cfg].WN) return MTD_EINVAL;       // (a retired number: no plan has it)
+    const dim3 grid(pl.nsplit, (a.N / (32 * pl.WN)) * p.nCt, pl.ntg);
+    const int ndw = (np == 2 || r.ns_first) ? 2 : 1;      // gradients written
+    const int prof = mtd_prof_begin(1, pl.cfg, pl.nsplit, np * geom_pixels(g), a.N, a.C, p.T, s,
+                                    4.0 * (np * ((double)geom_pixels(g) * a.N + (double)g.B * g.IH * g.IW * a.C) + (double)ndw * p.T * a.N * a.C));
+    WgradWinoParams wp;
+    switch (pl.cfg) {       // (templates are instantiated, and their kernels laid out in the code object, in the order of these cases)
+        case WCFG_T9: MTD_LAUNCH((wgrad_kernel<1, 1, 9>), grid, dim3(256), 0, s, p); break;
+        case WCFG_T4: MTD_LAUNCH((wgrad_kernel<1, 1, 4>), grid, dim3(256), 0, s, p); break;
+        case WCFG_64_T1: MTD_LAUNCH((wgrad_kernel<2, 2, 1>), grid, dim3(256), 0, s, p); break;
+        case WCFG_T8: MTD_LAUNCH((wgrad_kernel<1, 1, 8>), grid, dim3(256), 0, s, p); break;
+        case WCFG_T3: MTD_LAUNCH((wgrad_kernel<1, 1, 3>), grid, dim3(256), 0, s, p); break;
+        case WCFG_ROW3: WGRAD_LAUNCH_ROW3(1); break;
+        case WCFG_ROW3_REV: WGRAD_LAUNCH_ROW3(-1); break;
+        case WCFG_ROW1:
+            if (pl.nw == 8) MTD_LAUNCH((wgrad_row_kernel<1, 1, 1, 8>), grid, dim3(512), 0, s, p);
+            else MTD_LAUNCH((wgrad_row_kernel<1, 1, 1, 4>), grid, dim3(256), 0, s, p);
+            break;
+        case WCFG_BLK8: MTD_LAUNCH((wgrad_blk_kernel<8, 4>), grid, dim3(256), 0, s, p); break;
+        case WCFG_BLK4:
+            if (pl.nw == 8) MTD_LAUNCH((wgrad_blk_kernel<4, 8>), grid, dim3(512), 0, s, p);
+            else MTD_LAUNCH((wgrad_blk_kernel<4, 4>), grid, dim3(256), 0, s, p);
+            break;
+        case WCFG_BLK2:
+            if (pl.nw == 8) MTD_LAUNCH((wgrad_blk_kernel<2, 8>), grid, dim3(512), 0, s, p);
+            else MTD_LAUNCH((wgrad_blk_kernel<2, 4>), grid, dim3(256), 0, s, p);
+            break;
+        case WCFG_TAPS: MTD_LAUNCH(wgrad_taps_kernel, grid, dim3(256), 0, s, p); break;
+        case WCFG_S2:
+            if (wgrad_lab().s2_db) MTD_LAUNCH((wgrad_s2_kernel<true>), grid, dim3(256), 0, s, p);
+            else MTD_LAUNCH((wgrad_s2_kernel<false>), grid, dim3(256), 0, s, p);
+            break;
+        case WCFG_T1: MTD_LAUNCH((wgrad_kernel<1, 1, 1>), grid, dim3(256), 0, s, p); break;
+        case WCFG_64_T3: MTD_LAUNCH((wgrad_kernel<2, 2, 3>), grid, dim3(256), 0, s, p); break;
+        case WCFG_WINO:
+            fill_wino_params(wp, p, pl, r);
+            MTD_LAUNCH(wgrad_wino_kernel, dim3(grid.x, grid.y), dim3(512), 0, s, wp);
+            break;
+        case WCFG_WINO_S2:
+            fill_wino_params(wp, p, pl, r);
+            MTD_LAUNCH(wgrad_wino_s2_kernel, dim3(grid.x, (unsigned)wgrad_wino_s2_blocks(a)), dim3(512), 0, s, wp);
+            break;
+        case WCFG_WINO32:
+            fill_wino_params(wp, p, pl, r);
+            MTD_LAUNCH(wgrad_wino32_kernel, dim3(grid.x), dim3(512), 0, s, wp, g.tap_dy < 0 ? 1 : 0);
+            break;
+        default: break;
+    }
+    mtd_prof_end(prof, s);
+    MTD_LAUNCH_CHECK();
+    return MTD_OK;
+}
+#undef WGRAD_LAUNCH_ROW3
+
+// tuning hooks (mtd_conv_wgrad_override, mtd_conv_wgrad_pair_mode: tests, lab); every planner call gets a copy
+static WgradForce g_wforce;
+static WgradForce wgrad_force() {
+    WgradForce f = g_wforce;
+    const int nw = wgrad_lab().nw;
+    if (nw == 4 || nw == 8) f.nw = nw;
+    return f;
+}
+
+extern "C" int mtd_conv_wgrad_override(int cfg, int nsplit) {
+    g_wforce.cfg = cfg;
+    g_wforce.split = nsplit;
+    return MTD_OK;
+}
+
+// 0: never pair, 1: the default rule, 2: Winograd kernels only, 3: every kernel that has the pair form, -1: back to the
+// environment's choice.  Returns the previous mode.
+extern "C" int mtd_conv_wgrad_pair_mode(int mode) {
+    const int prev = g_wforce.pair_mode;
+    g_wforce.pair_mode = mode;
+    return prev;
 }
 
 extern "C" size_t mtd_conv_wgrad_ws_bytes(const mtd_wgrad_args* a) {
     if (!a || check_wargs(*a) != MTD_OK) return 0;
-    if (is_direct(*a)) return wgrad_ws_floats(*a, mtd_direct_wgrad_nslab(a)) * sizeof(float);
-    WPlan pl = make_wplan(*a);
-    return wgrad_ws_floats(*a, pl.nsplit) * sizeof(float);
+    const int nsplit = is_direct(*a) ? mtd_direct_wgrad_nslab(a) : make_wplan(*a, 1, wgrad_force()).nsplit;
+    return wgrad_ws_floats(*a, nsplit) * sizeof(float);
 }
 
-// The plan's kernel for these arguments: index into the profiler's weight-gradient name table (16 = the Winograd kernel, which
-// executes 4/9 of the layer's multiplications), -1 for the direct (vector-ALU) kernels, MTD_EINVAL for invalid arguments.
+// The plan's kernel for these arguments: index into the profiler's weight-gradient name table (WgradCfg; 16 = the Winograd kernel,
+// which executes 4/9 of the layer's multiplications), -1 for the direct (vector-ALU) kernels, MTD_EINVAL for invalid arguments.
 // Host-side flop accounting (kernels.wgrad) asks this instead of mirroring the plan.
 extern "C" int mtd_conv_wgrad_plan_cfg(const mtd_wgrad_args* a) {
     if (!a || check_wargs(*a) != MTD_OK) return MTD_EINVAL;
     if (is_direct(*a)) return -1;
-    return make_wplan(*a).cfg;
+    return make_wplan(*a, 1, wgrad_force()).cfg;
 }
 
-// plans whose kernels implement the pair form (pair_select): wgrad_kernel<> (0-6), the block-window kernels (10-12), the all-taps
-// kernel (13), the stride-2 halo-window kernel (15).  (16, the Winograd kernel, has its own: mtd_conv_wgrad_pair.)
-static bool wgrad_cfg_pairs(int cfg) { return (cfg >= 0 && cfg < NWCFG) || (cfg >= 10 && cfg <= 13) || cfg == 15; }
+extern "C" int mtd_conv_wgrad_half_scale_ok(const mtd_wgrad_args* a) { return a && wgrad_half_scale_ok(*a, wgrad_force()) ? 1 : 0; }
 
 // the slab-producing kernel of one layer; fills p, nsplit, direct
-// (rows != nullptr: also run the forward row transform `rows` describes, inside the same launch if the plan is the row-window
-// kernel on one (n, c) tile -- *rows_done says whether it was)
-// (pair: a describes ONE of two equal problems laid out back to back in p / q; the launch covers both, see WgradParams::pair_ns)
-// plans whose kernels apply mtd_wgrad_args.half_scale: wgrad_kernel<> (0-6), the block-window kernels (10-12), the all-taps kernel (13)
-static bool wgrad_cfg_half_scale(int cfg) { return (cfg >= 0 && cfg < NWCFG) || (cfg >= 10 && cfg <= 13); }
-
-extern "C" int mtd_conv_wgrad_half_scale_ok(const mtd_wgrad_args* a) {
-    if (!a || !a->half_scale || check_wargs(*a) != MTD_OK || is_direct(*a)) return 0;
-    return wgrad_cfg_half_scale(make_wplan(*a).cfg) ? 1 : 0;
-}
-
+// (rows, rows_done: see wgrad_launch)
+// (half != nullptr: a describes ONE of two equal problems laid out back to back in p / q, *half is its plan (wgrad_pair_plan); the
+// launch covers both, see WgradParams::pair_ns)
 static int wgrad_partial(const mtd_wgrad_args* a, void* stream, WgradParams& p, int& nsplit, bool& direct_out,
-                         const RowsArgs* rows = nullptr, bool* rows_done = nullptr, bool pair = false) {
+                         const RowsArgs* rows = nullptr, bool* rows_done = nullptr, const WPlan* half = nullptr) {
     if (!a) return MTD_EINVAL;
-    static const int env_nw = [] { const char* e = mtd_lab_env("MTD_WGRAD_NW"); return e ? atoi(e) : 0; }();
-    if (env_nw == 4 || env_nw == 8) g_wforce_nw = env_nw;
     int rc = check_wargs(*a);
     if (rc != MTD_OK) return rc;
     const bool direct = is_direct(*a);
     direct_out = direct;
     WPlan pl{};
-    if (direct) nsplit = mtd_direct_wgrad_nslab(a);
-    else if (!pair) { pl = make_wplan(*a); nsplit = pl.nsplit; }
-    // mtd_wgrad_args.half_scale: the register-operand kernels only (their K loops walk whole 32-pixel chunks of one half)
-    if (a->half_scale && (direct || pair || rows || !wgrad_cfg_half_scale(pl.cfg))) return MTD_EINVAL;
-    if (pair) {
-        if (direct) return MTD_EINVAL;
-        pl = make_wplan(*a, 2);
-        if (!wgrad_cfg_pairs(pl.cfg)) return MTD_EINVAL;
+    if (half) pl = *half;
+    else if (!direct) pl = make_wplan(*a, 1, wgrad_force());
+    if (a->half_scale && (direct || half || rows || !kWgradCfg[pl.cfg].half_scale)) return MTD_EINVAL;
+    if (half) {
+        if (direct || !kWgradCfg[pl.cfg].pairs) return MTD_EINVAL;
         p.pair_ns = pl.nsplit;
         p.pair_p_off = geom_pixels(a->g) * a->p_ld;
         p.pair_q_off = (long long)a->g.B * a->g.IH * a->g.IW * a->q_ld;
         pl.nsplit *= 2;
-        nsplit = pl.nsplit;
     }
+    nsplit = direct ? mtd_direct_wgrad_nslab(a) : pl.nsplit;
     if (!a->ws || a->ws_bytes < wgrad_ws_floats(*a, nsplit) * sizeof(float)) return MTD_EWS;
-    p.a = *a;
-    p.M = (int)geom_pixels(a->g);
-    p.T = a->g.TH * a->g.TW;
-    p.nslab = nsplit;
-    p.slab_stride = (long long)p.T * a->N * a->C + a->N;
-    {
-        const mtd_geom& gg = a->g;
-        for (int t = 0; t < gg.TH * gg.TW; ++t) {
-            const int ty = t / gg.TW, tx = t % gg.TW;
-            p.tap_dy[t] = ty * gg.tap_dy;
-            p.tap_dx[t] = tx * gg.tap_dx;
-            p.tap_delta[t] = (int)((((long long)(ty * gg.tap_dy) * gg.IW + tx * gg.tap_dx) * a->q_ld) * 4);
-        }
-        const long long pb = (((long long)p.M - 1) * a->p_ld + a->N) * 4;
-        const long long qb = (((long long)gg.B * gg.IH * gg.IW - 1) * a->q_ld + a->C) * 4;
-        if (pb >= (1ll << 31) || qb >= (1ll << 31)) return MTD_EINVAL;
-        p.p_bytes = (unsigned)pb;
-        p.q_bytes = (unsigned)qb;
-    }
-    hipStream_t s = (hipStream_t)stream;
+    rc = fill_wgrad_params(p, *a, nsplit);
+    if (rc != MTD_OK) return rc;
     if (direct) {
         p.ppw = 0;
         p.nCt = 1;
         int ns2 = 0;
         rc = mtd_direct_wgrad_launch(a, &ns2, p.slab_stride, stream);
         if (rc != MTD_OK) return rc;
-        if (ns2 != nsplit) return MTD_EINVAL;
-    } else {
-        p.ppw = pl.ppw;
-        p.nCt = a->C / (32 * pl.WC);
-        dim3 grid(pl.nsplit, (a->N / (32 * pl.WN)) * p.nCt, pl.ntg);
-        const int np = pair ? 2 : 1;         // problems in this launch
-        const int prof = mtd_prof_begin(1, pl.cfg, pl.nsplit, np * geom_pixels(a->g), a->N, a->C, a->g.TH * a->g.TW, s,
-                                            4.0 * np * ((double)geom_pixels(a->g) * a->N + (double)a->g.B * a->g.IH * a->g.IW * a->C + (double)a->g.TH * a->g.TW * a->N * a->C));
-        // Row-window kernel: 64 KB of dynamic LDS nobody uses caps it at ONE workgroup (one wave per SIMD) per CU.  Alone in
-        // a stream that changes nothing (generator step: 31.7 us per launch either way); in the full step, where it runs on a
-        // side stream beside the data-gradient chain, a second workgroup on a CU took the slots of the other stream's
-        // kernel: 44.47 -> 44.03 ms per step (three A/B runs each, tools/wgrad_pad_full.sh).  MTD_WGRAD_LDS_PAD=0 is the old launch.
-        static const unsigned lds_pad = [] { const char* e = mtd_lab_env("MTD_WGRAD_LDS_PAD"); return e ? (unsigned)atoi(e) : 65536u; }();
-        if (pl.cfg == 16) {
-            WgradWinoParams wp;
-            wp.w = p;
-            wp.tiles_x = a->g.OW / 2;
-            wp.tiles_per_image = (a->g.OH / 2) * wp.tiles_x;
-            wp.ntiles = a->g.B * wp.tiles_per_image;
-            wp.chunks_per_split = pl.ppw;
-            wp.ns_first = wp.first_tiles = 0;
-            wp.p_add = nullptr;
-            MTD_LAUNCH(wgrad_wino_kernel, dim3(pl.nsplit, (a->N / 64) * (a->C / 64)), dim3(512), 0, s, wp);
-            mtd_prof_end(prof, s);
-            MTD_LAUNCH_CHECK();
-            return MTD_OK;
-        }
-        if (pl.cfg == 19) {
-            WgradWinoParams wp;
-            wp.w = p;
-            wp.tiles_x = a->g.OW / 2;
-            wp.tiles_per_image = (a->g.OH / 2) * wp.tiles_x;
-            wp.ntiles = a->g.B * wp.tiles_per_image;
-            wp.chunks_per_split = pl.ppw;
-            wp.ns_first = wp.first_tiles = 0;
-            wp.p_add = nullptr;
-            MTD_LAUNCH(wgrad_wino32_kernel, dim3(pl.nsplit), dim3(512), 0, s, wp, a->g.tap_dy < 0 ? 1 : 0);
-            mtd_prof_end(prof, s);
-            MTD_LAUNCH_CHECK();
-            return MTD_OK;
-        }
-        if (pl.cfg == 18) {
-            WgradWinoParams wp;
-            wp.w = p;
-            wp.tiles_x = (a->g.OW + 2) / 3;
-            wp.tiles_per_image = ((a->g.OH + 2) / 3) * wp.tiles_x;
-            wp.ntiles = a->g.B * wp.tiles_per_image;
-            wp.chunks_per_split = pl.ppw;
-            wp.ns_first = wp.first_tiles = 0;
-            wp.p_add = nullptr;
-            MTD_LAUNCH(wgrad_wino_s2_kernel, dim3(pl.nsplit, (unsigned)wgrad_wino_s2_blocks(*a)), dim3(512), 0, s, wp);
-            mtd_prof_end(prof, s);
-            MTD_LAUNCH_CHECK();
-            return MTD_OK;
-        }
-        switch (pl.cfg) {
-            case 0: MTD_LAUNCH((wgrad_kernel<1, 1, 9>), grid, dim3(256), 0, s, p); break;
-            case 1: MTD_LAUNCH((wgrad_kernel<1, 1, 4>), grid, dim3(256), 0, s, p); break;
-            case 2: MTD_LAUNCH((wgrad_kernel<2, 2, 1>), grid, dim3(256), 0, s, p); break;
-            case 3: MTD_LAUNCH((wgrad_kernel<1, 1, 8>), grid, dim3(256), 0, s, p); break;
-            case 4: MTD_LAUNCH((wgrad_kernel<1, 1, 3>), grid, dim3(256), 0, s, p); break;
-            case 7: if (pl.nw == 8) MTD_LAUNCH((wgrad_row_kernel<3, 3, 1, 8>), grid, dim3(512), 0, s, p);
-                    else if (rows && grid.y == 1 && grid.z == 1) {
-                        const dim3 fg(grid.x + (unsigned)((rows->npairs + 7) / 8));
-                        MTD_LAUNCH((wgrad_row_rfft_kernel<1>), fg, dim3(256), 0, s, p, (int)grid.x, *rows);
-                        *rows_done = true;
-                    } else MTD_LAUNCH((wgrad_row_kernel<3, 3, 1, 4>), grid, dim3(256), lds_pad, s, p);
-                    break;
-            case 8: if (pl.nw == 8) MTD_LAUNCH((wgrad_row_kernel<3, 3, -1, 8>), grid, dim3(512), 0, s, p);
-                    else if (rows && grid.y == 1 && grid.z == 1) {
-                        const dim3 fg(grid.x + (unsigned)((rows->npairs + 7) / 8));
-                        MTD_LAUNCH((wgrad_row_rfft_kernel<-1>), fg, dim3(256), 0, s, p, (int)grid.x, *rows);
-                        *rows_done = true;
-                    } else MTD_LAUNCH((wgrad_row_kernel<3, 3, -1, 4>), grid, dim3(256), lds_pad, s, p);
-                    break;
-            case 9: if (pl.nw == 8) MTD_LAUNCH((wgrad_row_kernel<1, 1, 1, 8>), grid, dim3(512), 0, s, p);
-                    else MTD_LAUNCH((wgrad_row_kernel<1, 1, 1, 4>), grid, dim3(256), 0, s, p);
-                    break;
-            case 10: MTD_LAUNCH((wgrad_blk_kernel<8, 4>), grid, dim3(256), 0, s, p); break;
-            case 11: if (pl.nw == 8) MTD_LAUNCH((wgrad_blk_kernel<4, 8>), grid, dim3(512), 0, s, p);
-                     else MTD_LAUNCH((wgrad_blk_kernel<4, 4>), grid, dim3(256), 0, s, p);
-                     break;
-            case 12: if (pl.nw == 8) MTD_LAUNCH((wgrad_blk_kernel<2, 8>), grid, dim3(512), 0, s, p);
-                     else MTD_LAUNCH((wgrad_blk_kernel<2, 4>), grid, dim3(256), 0, s, p);
-                     break;
-            case 13: MTD_LAUNCH(wgrad_taps_kernel, grid, dim3(256), 0, s, p); break;
-            case 15: {
-                static const int env_db = [] { const char* e = mtd_lab_env("MTD_WGRAD_S2_DB"); return e ? atoi(e) : 0; }();
-                if (env_db) MTD_LAUNCH((wgrad_s2_kernel<true>), grid, dim3(256), 0, s, p);
-                else MTD_LAUNCH((wgrad_s2_kernel<false>), grid, dim3(256), 0, s, p);
-                break;
-            }
-            case 5: MTD_LAUNCH((wgrad_kernel<1, 1, 1>), grid, dim3(256), 0, s, p); break;
-            default: MTD_LAUNCH((wgrad_kernel<2, 2, 3>), grid, dim3(256), 0, s, p); break;
-        }
-        mtd_prof_end(prof, s);
-        MTD_LAUNCH_CHECK();
+        return ns2 == nsplit ? MTD_OK : MTD_EINVAL;
     }
-    return MTD_OK;
+    p.ppw = pl.ppw;
+    p.nCt = a->C / (32 * pl.WC);
+    return wgrad_launch(pl, p, (hipStream_t)stream, half ? 2 : 1, WinoRanges{}, rows, rows_done);
 }
 
 extern "C" int mtd_conv_wgrad_slabs(const mtd_wgrad_args* a, int* nslab, long long* slab_stride, void* stream) {
@@ -1620,10 +1393,6 @@ extern "C" int mtd_conv_wgrad_reduce_multi(const mtd_wgrad_reduce_desc* table_de
     return MTD_OK;
 }
 
-static int wgrad_fused_reduce_enabled() {
-    static const int env_fused = [] { const char* e = mtd_lab_env("MTD_WGRAD_FUSED_REDUCE"); return e ? atoi(e) : 1; }();
-    return env_fused;
-}
 static int wgrad_reduce_slabs_impl(const WgradParams& p, const float* cur, int ns, float* next, bool direct, hipStream_t s, float* dw2);
 static int wgrad_reduce_slabs(const WgradParams& p, const float* cur, int ns, float* next, bool direct, hipStream_t s) {
     return wgrad_reduce_slabs_impl(p, cur, ns, next, direct, s, nullptr);
@@ -1631,7 +1400,7 @@ static int wgrad_reduce_slabs(const WgradParams& p, const float* cur, int ns, fl
 // the 2 ns slabs of a pair launch: slabs 0 .. ns - 1 into p.a.dw, the others into dw2, both bias rows into p.a.db
 static int wgrad_reduce_pair(WgradParams& p, const float* cur, int ns, float* next, float* dw2, int accumulate, hipStream_t s) {
     const long long units = p.slab_stride / 4;
-    if (ns <= GS || (wgrad_fused_reduce_enabled() && ns <= 1024 && units <= 16 * 4096))
+    if (ns <= GS || (wgrad_lab().fused_reduce && ns <= 1024 && units <= 16 * 4096))
         return wgrad_reduce_slabs_impl(p, cur, ns, next, false, s, dw2);                    // one launch for both
     int rc = wgrad_reduce_slabs_impl(p, cur, ns, next, false, s, nullptr);
     if (rc != MTD_OK) return rc;
@@ -1655,75 +1424,19 @@ extern "C" int mtd_conv_wgrad(const mtd_wgrad_args* a, void* stream) {
 // [0, b_first) give a->dw, images [b_first, B) give dw2; both bias gradients go to a->db (the second is accumulated).
 // The slab-producing kernel runs once with its slices aligned to the image ranges -- twice the work per workgroup of two
 // launches that each fill the chip, i.e. half the prologues, epilogues, slabs -- and each range's slabs are summed into
-// its own gradient.  Winograd plan only (wgrad_wino_kernel); mtd_conv_wgrad_pair_ok says whether a layer qualifies.
-static int g_wpair_mode = -1;            // -1: MTD_WGRAD_PAIR (default 1); set by mtd_conv_wgrad_pair_mode (tests, lab)
-static bool wgrad_pair_plan(const mtd_wgrad_args& a, int b_first, int& ns_half, int& cps) {
-    if (check_wargs(a) != MTD_OK || is_direct(a)) return false;
-    if (b_first <= 0 || 2 * b_first != a.g.B) return false;
-    static const int env_pair_default = [] { const char* e = mtd_lab_env("MTD_WGRAD_PAIR"); return e ? atoi(e) : 1; }();
-    const int env_pair = g_wpair_mode >= 0 ? g_wpair_mode : env_pair_default;
-    if (!env_pair) return false;
-    mtd_wgrad_args h = a;
-    h.g.B = b_first;
-    const int cfg = make_wplan(h).cfg;
-    if (cfg == 18) {                       // the stride-2 Winograd kernel: the pair form of cfg 16 (slices aligned to the image ranges)
-        const long long blocks = wgrad_wino_s2_blocks(a);
-        const long long chunks = (wgrad_wino_s2_tiles(a, b_first) + WGW_T - 1) / WGW_T;
-        long long ns = (128 + blocks - 1) / blocks;
-        if (ns > chunks / 4) ns = chunks / 4;
-        if (ns < 1) ns = 1;
-        const long long c = (chunks + ns - 1) / ns;
-        ns = (chunks + c - 1) / c;
-        ns_half = -(int)ns;                // (negative: cfg 18)
-        cps = (int)c;
-        return true;
-    }
-    if (cfg != 16) {                       // the general kernels: planned inside wgrad_partial
-        // By default only the stride-2 halo-window kernel (cfg 15: `down` layers with output maps of at least 8x8: 14-21 us less
-        // per pair).  The small-map kernels lose: their single launches have one pixel split and write the gradient themselves,
-        // a pair launch has two slabs per (n, c) tile and a reduce (down4 132 -> 210 us, down6 26 -> 102 us, conv5x 47 -> 66 us;
-        // tools/wgrad_pair_probe.py).  MTD_WGRAD_PAIR=2: Winograd kernel only, 3: every kernel with the pair form (lab, tests).
-        if (env_pair == 2 || (env_pair != 3 && cfg != 15)) return false;
-        ns_half = cps = 0;
-        return wgrad_cfg_pairs(cfg);
-    }
-    const long long blocks = wgrad_wino_blocks(a);
-    const long long chunks = (wgrad_wino_tiles(a, b_first) + WGW_T - 1) / WGW_T;
-    long long ns = (128 + blocks - 1) / blocks;                  // the two ranges together: about one workgroup per CU
-    if (ns > chunks / 4) ns = chunks / 4;
-    if (ns < 1) ns = 1;
-    const long long c = (chunks + ns - 1) / ns;
-    ns = (chunks + c - 1) / c;
-    ns_half = (int)ns;
-    cps = (int)c;
-    return true;
-}
-
-// 0: never pair, 1: the default rule, 2: Winograd kernel only, 3: every kernel that has the pair form, -1: back to the
-// environment's choice.  Returns the previous mode.
-extern "C" int mtd_conv_wgrad_pair_mode(int mode) {
-    const int prev = g_wpair_mode;
-    g_wpair_mode = mode;
-    return prev;
-}
-
+// its own gradient.  wgrad_pair_plan (conv_wgrad_plan.h) says which layers qualify and on which kernel.
+//
 // 0: no pair form; 1: mtd_conv_wgrad_pair; 2: also mtd_conv_wgrad_pair_sum (the Winograd plan: a second cotangent added on load)
 extern "C" int mtd_conv_wgrad_pair_ok(const mtd_wgrad_args* a, int b_first) {
-    int ns, cps;
-    if (!a || !wgrad_pair_plan(*a, b_first, ns, cps)) return 0;
-    return ns > 0 ? 2 : 1;                 // (the stride-2 Winograd kernel, ns < 0, has no second cotangent)
+    if (!a) return 0;
+    const WPairPlan pp = wgrad_pair_plan(*a, b_first, wgrad_force());
+    return !pp.ok ? 0 : (pp.half.cfg == WCFG_WINO ? 2 : 1);
 }
 
 extern "C" size_t mtd_conv_wgrad_pair_ws_bytes(const mtd_wgrad_args* a, int b_first) {
-    int ns, cps;
-    if (!a || !wgrad_pair_plan(*a, b_first, ns, cps)) return 0;
-    if (ns == 0) {
-        mtd_wgrad_args h = *a;
-        h.g.B = b_first;
-        ns = make_wplan(h, 2).nsplit;
-    }
-    if (ns < 0) ns = -ns;
-    return wgrad_ws_floats(*a, 2 * ns) * sizeof(float);
+    if (!a) return 0;
+    const WPairPlan pp = wgrad_pair_plan(*a, b_first, wgrad_force());
+    return pp.ok ? wgrad_ws_floats(*a, 2 * pp.half.nsplit) * sizeof(float) : 0;
 }
 
 extern "C" int mtd_conv_wgrad_pair_sum(const mtd_wgrad_args* a, const float* p_add, float* dw2, int b_first, void* stream);
@@ -1734,55 +1447,31 @@ extern "C" int mtd_conv_wgrad_pair(const mtd_wgrad_args* a, float* dw2, int b_fi
 // as mtd_conv_wgrad_pair with the gradients taken from a->p + p_add (p_add: same shape, pixel stride and alignment as a->p; NULL:
 // none).  Only where mtd_conv_wgrad_pair_ok says 2.
 extern "C" int mtd_conv_wgrad_pair_sum(const mtd_wgrad_args* a, const float* p_add, float* dw2, int b_first, void* stream) {
-    int ns_half = 0, cps = 0;
-    if (!a || !dw2 || a->half_scale || !wgrad_pair_plan(*a, b_first, ns_half, cps)) return MTD_EINVAL;
-    if (p_add && (ns_half <= 0 || !aligned16(p_add))) return MTD_EINVAL;
-    const bool s2w = ns_half < 0;          // the stride-2 Winograd kernel (cfg 18)
-    if (s2w) ns_half = -ns_half;
-    if (ns_half == 0) {                    // one of the general kernels over both problems
+    if (!a || !dw2 || a->half_scale) return MTD_EINVAL;
+    const WPairPlan pp = wgrad_pair_plan(*a, b_first, wgrad_force());
+    if (!pp.ok) return MTD_EINVAL;
+    if (p_add && (pp.half.cfg != WCFG_WINO || !aligned16(p_add))) return MTD_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    WgradParams p;
+    WPlan pl = pp.half;
+    pl.nsplit *= 2;
+    if (kWgradCfg[pl.cfg].pairs) {         // one of the general kernels over both problems
         mtd_wgrad_args h = *a;
         h.g.B = b_first;
-        WgradParams p;
         int ns = 0;
         bool direct = false;
-        int rc = wgrad_partial(&h, stream, p, ns, direct, nullptr, nullptr, true);
+        const int rc = wgrad_partial(&h, stream, p, ns, direct, nullptr, nullptr, &pp.half);
         if (rc != MTD_OK) return rc;
-        return wgrad_reduce_pair(p, a->ws, ns / 2, a->ws + (long long)ns * p.slab_stride, dw2, a->accumulate, (hipStream_t)stream);
+    } else {                               // a Winograd kernel over the whole batch, its slices aligned to the image ranges
+        if (!a->ws || a->ws_bytes < wgrad_ws_floats(*a, pl.nsplit) * sizeof(float)) return MTD_EWS;
+        int rc = fill_wgrad_params(p, *a, pl.nsplit);
+        if (rc != MTD_OK) return rc;
+        p.ppw = pl.ppw;
+        p.nCt = a->C / (32 * pl.WC);
+        rc = wgrad_launch(pl, p, s, 1, WinoRanges{pp.half.nsplit, b_first, p_add});
+        if (rc != MTD_OK) return rc;
     }
-    const int nsplit = 2 * ns_half;
-    if (!a->ws || a->ws_bytes < wgrad_ws_floats(*a, nsplit) * sizeof(float)) return MTD_EWS;
-    WgradWinoParams wp;
-    WgradParams& p = wp.w;
-    p.a = *a;
-    p.M = (int)geom_pixels(a->g);
-    p.T = s2w ? 16 : 9;
-    p.nslab = nsplit;
-    p.slab_stride = (long long)p.T * a->N * a->C + a->N;
-    for (int t = 0; t < 16; ++t) p.tap_dy[t] = p.tap_dx[t] = p.tap_delta[t] = 0;
-    {
-        const long long pb = (((long long)p.M - 1) * a->p_ld + a->N) * 4;
-        const long long qb = (((long long)a->g.B * a->g.IH * a->g.IW - 1) * a->q_ld + a->C) * 4;
-        if (pb >= (1ll << 31) || qb >= (1ll << 31)) return MTD_EINVAL;
-        p.p_bytes = (unsigned)pb;
-        p.q_bytes = (unsigned)qb;
-    }
-    p.ppw = cps;
-    p.nCt = a->C / 64;
-    wp.tiles_x = s2w ? (a->g.OW + 2) / 3 : a->g.OW / 2;
-    wp.tiles_per_image = (s2w ? (a->g.OH + 2) / 3 : a->g.OH / 2) * wp.tiles_x;
-    wp.ntiles = a->g.B * wp.tiles_per_image;
-    wp.chunks_per_split = cps;
-    wp.ns_first = ns_half;
-    wp.first_tiles = b_first * wp.tiles_per_image;
-    wp.p_add = p_add;
-    hipStream_t s = (hipStream_t)stream;
-    const int prof = mtd_prof_begin(1, s2w ? 18 : 16, nsplit, geom_pixels(a->g), a->N, a->C, p.T, s,
-                                    4.0 * ((double)geom_pixels(a->g) * a->N + (double)a->g.B * a->g.IH * a->g.IW * a->C + 2.0 * p.T * a->N * a->C));
-    if (s2w) MTD_LAUNCH(wgrad_wino_s2_kernel, dim3(nsplit, (unsigned)wgrad_wino_s2_blocks(*a)), dim3(512), 0, s, wp);
-    else MTD_LAUNCH(wgrad_wino_kernel, dim3(nsplit, (a->N / 64) * (a->C / 64)), dim3(512), 0, s, wp);
-    mtd_prof_end(prof, s);
-    MTD_LAUNCH_CHECK();
-    return wgrad_reduce_pair(p, a->ws, ns_half, a->ws + (long long)nsplit * p.slab_stride, dw2, a->accumulate, s);
+    return wgrad_reduce_pair(p, a->ws, pp.half.nsplit, a->ws + (long long)pl.nsplit * p.slab_stride, dw2, a->accumulate, s);
 }
 
 // staged, order-fixed reduction of ns slabs at cur into p.a.dw / p.a.db (staging area: next)
@@ -1795,16 +1484,14 @@ static int wgrad_reduce_slabs_impl(const WgradParams& p, const float* cur, int n
     const long long units = vec ? count / 4 : count;
     // 16 < ns <= 1024 slabs of a layer small enough that 16-column workgroups still fill the chip's launch slots quickly:
     // one fused launch.  (Large layers have few slabs and keep the one-thread-per-float4 finish kernel.)
-    const int env_fused = wgrad_fused_reduce_enabled();
-    if (vec && env_fused && ns > 16 && ns <= 1024 && units <= 16 * 4096) {
+    if (vec && wgrad_lab().fused_reduce && ns > 16 && ns <= 1024 && units <= 16 * 4096) {
         const int bx = (int)((units + 15) / 16);
         if (ns > 128) hipLaunchKernelGGL((wgrad_reduce_finish_kernel<8>), dim3(bx, dw2 ? 2 : 1), dim3(1024), 0, s, p, cur, ns, p.slab_stride, dw2);
         else hipLaunchKernelGGL((wgrad_reduce_finish_kernel<4>), dim3(bx, dw2 ? 2 : 1), dim3(256), 0, s, p, cur, ns, p.slab_stride, dw2);
         MTD_LAUNCH_CHECK();
         return MTD_OK;
     }
-    static const int env_scalar2 = [] { const char* e = mtd_lab_env("MTD_WGRAD_SCALAR2"); return e ? atoi(e) : 1; }();
-    if (env_scalar2 && !vec && !dw2 && ns > GS && ns <= 16 * GS) {          // thin layers: both stages in one launch (same association)
+    if (wgrad_lab().scalar2 && !vec && !dw2 && ns > GS && ns <= 16 * GS) {          // thin layers: both stages in one launch (same association)
         hipLaunchKernelGGL(wgrad_finish_scalar2_kernel, dim3((unsigned)((count + 15) / 16)), dim3(256), 0, s, p, cur, ns, p.slab_stride, GS);
         MTD_LAUNCH_CHECK();
         return MTD_OK;

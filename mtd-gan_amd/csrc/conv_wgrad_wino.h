@@ -23,7 +23,8 @@
 // Domain: forward-oriented 3x3 / stride 1 / pad 1 geometry, even map sides, N and C multiples of 64.
 // Roofline: fp32 MFMA; executed flops 2 M N C 4 of the algorithmic 2 M N C 9.
 
-constexpr int WGW_T = 8;                       // tiles per chunk
+#include "conv_wgrad_plan.h"                   // WGW_T, tiles per chunk, and the kernel's domain wgrad_wino_ok (conv_wgrad.hip has
+                                               // included it at file scope already: this line only names where they are)
 constexpr int WGW_PL = WGW_T * 64 + 4;         // plane stride (floats) of one position: 16 bytes of skew per position keeps the four
                                                // quad lanes' 16-byte stores (positions 4 i' + j) on different banks
 constexpr int WGW_BUF = 2 * 16 * WGW_PL;       // one chunk buffer: U planes then V planes
@@ -353,24 +354,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino_kernel(const WgradWinoParam
     }
 }
 
-// the kernel's domain
-bool wgrad_wino_ok(const mtd_wgrad_args& a) {
-    const mtd_geom& g = a.g;
-    if (g.TH != 3 || g.TW != 3 || g.in_sy != 1 || g.in_sx != 1 || g.tap_dy != 1 || g.tap_dx != 1 || g.off_y != -1 || g.off_x != -1) return false;
-    if (g.ky0 != 0 || g.kx0 != 0 || g.ky_step != 1 || g.kx_step != 1 || g.KW != 3) return false;
-    if (g.IH != g.OH || g.IW != g.OW || (g.OH & 1) || (g.OW & 1)) return false;
-    if ((a.N % 64) || (a.C % 64)) return false;
-    if (!aligned16(a.p) || !aligned16(a.q) || (a.p_ld % 4) || (a.q_ld % 4)) return false;
-    return true;
-}
-
 // (A Winograd F(2x4, 3x3) form of this kernel -- the transpose of wino_conv_kernel<., ., 6>, 24 positions on a 64 x 32 block --
 // was built in round 4, measured slower twice (132-138 against 102 us per launch on the large layers, step 31.08 against 29.94 ms:
 // 24 MFMAs per chunk and 32 channels to this kernel's 32 and 64, a heavier cotangent transform per MFMA) and removed in round 6;
 // docs/LAB_NOTES_r3_r5.md has the numbers, the history has the kernel.)
-constexpr int wgrad_wino_px(const mtd_wgrad_args&) { return 4; }
-// (n, c) blocks and tiles of a layer in the form it takes
-inline long long wgrad_wino_blocks(const mtd_wgrad_args& a) { return (long long)(a.N / 64) * (a.C / 64); }
-inline long long wgrad_wino_tiles(const mtd_wgrad_args& a, long long images) {
-    return images * (a.g.OH / 2) * (a.g.OW / 2);
-}

@@ -9,7 +9,7 @@
 //   * the transposed-conv layers (tap_d = -1: the decoder's ConvTranspose2d) differ only in which tap of the slab a position
 //     pair lands on (flipped).
 // Slab layout as everywhere: slab[(tap 32 + n) 32 + c], bias row at tap = 9.  Executed flops 2 M 32 32 4.
-constexpr int W32_T = 16;                        // tiles per chunk
+#include "conv_wgrad_plan.h"                     // W32_T, tiles per chunk, and the kernel's domain wgrad_wino32_ok
 constexpr int W32_PL = W32_T * 32 + 4;           // plane stride (floats) of one position
 constexpr int W32_BUF = 2 * 16 * W32_PL;         // one chunk buffer: U planes then V planes
 
@@ -213,17 +213,4 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino32_kernel(const WgradWinoPar
             slab[(long long)p.T * 32 * 32 + tid] = v;
         }
     }
-}
-
-// the kernel's domain: 3x3 / stride 1 / pad 1 in the forward (tap_d = +1, off = -1) or the transposed (tap_d = -1, off = +1) tap order,
-// N = C = 32, even height, width a multiple of 4 (tile rows of an even number of tiles)
-bool wgrad_wino32_ok(const mtd_wgrad_args& a) {
-    const mtd_geom& g = a.g;
-    if (g.TH != 3 || g.TW != 3 || g.in_sy != 1 || g.in_sx != 1 || g.tap_dy != g.tap_dx) return false;
-    if (!((g.tap_dy == 1 && g.off_y == -1 && g.off_x == -1) || (g.tap_dy == -1 && g.off_y == 1 && g.off_x == 1))) return false;
-    if (g.ky0 != 0 || g.kx0 != 0 || g.ky_step != 1 || g.kx_step != 1 || g.KW != 3) return false;
-    if (g.IH != g.OH || g.IW != g.OW || (g.OH & 1) || (g.OW & 3)) return false;
-    if (a.N != 32 || a.C != 32) return false;
-    if (!aligned16(a.p) || !aligned16(a.q) || (a.p_ld % 4) || (a.q_ld % 4)) return false;
-    return true;
 }

@@ -248,16 +248,3 @@ __global__ __launch_bounds__(512, 1) void wgrad_wino_s2_kernel(const WgradWinoPa
         }
     }
 }
-
-// the kernel's domain: the forward geometry of Conv2d(k4, s2, p1), N and C multiples of 64
-bool wgrad_wino_s2_ok(const mtd_wgrad_args& a) {
-    const mtd_geom& g = a.g;
-    if (g.TH != 4 || g.TW != 4 || g.in_sy != 2 || g.in_sx != 2 || g.tap_dy != 1 || g.tap_dx != 1 || g.off_y != -1 || g.off_x != -1) return false;
-    if (g.ky0 != 0 || g.kx0 != 0 || g.ky_step != 1 || g.kx_step != 1 || g.KW != 4) return false;
-    if (g.IH != 2 * g.OH || g.IW != 2 * g.OW) return false;
-    if ((a.N % 64) || (a.C % 64)) return false;
-    if (!aligned16(a.p) || !aligned16(a.q) || (a.p_ld % 4) || (a.q_ld % 4)) return false;
-    return true;
-}
-inline long long wgrad_wino_s2_blocks(const mtd_wgrad_args& a) { return (long long)(a.N / 64) * (4 * a.C / 64); }
-inline long long wgrad_wino_s2_tiles(const mtd_wgrad_args& a, long long images) { return images * ((a.g.OH + 2) / 3) * ((a.g.OW + 2) / 3); }

@@ -395,6 +395,8 @@ FLOP_COUNT = None
 _FFT_HALF_PLANE = 2.5 * 4096 * 12 / 2
 
 
+# Plan numbers of the weight-gradient kernels: enum WgradCfg and the table kWgradCfg of csrc/conv_wgrad_plan.h are the source;
+# these three and WGRAD_CONFIGS below mirror them (tests/test_wgrad_plan_cpu.py compares).
 WGRAD_CFG_WINO = 16                            # mtd_conv_wgrad_plan_cfg: wgrad_wino_kernel (F(2x2, 3x3); 17 was its F(2x4) form, removed in round 6)
 WGRAD_CFG_WINO_S2 = 18                         # wgrad_wino_s2_kernel: F(3x3, 2x2) over the four phases of a 4x4 / stride-2 layer
 WGRAD_CFG_WINO32 = 19                          # wgrad_wino32_kernel: F(2x2, 3x3) on the generator's 32 x 32 block
@@ -436,6 +438,7 @@ IGEMM_CONFIGS = ["igemm_kernel<2, 1, 4, 1>", "igemm_kernel<1, 1, 4, 1>", "igemm_
                  "wino_conv_multi_kernel<2, false, 6>", "wino_conv_multi_kernel<2, false, 4>", "wino_conv_multi_kernel<4, false, 4>",      # 34-37: two problems of
                  "wino_conv_multi_kernel<2, true, 4>",
                  "wino_c32_kernel<false, false, _Float16>", "wino_c32_kernel<true, false, _Float16>"]      # 38, 39: binary16 activation storage (whole-slice inference)                                                                                         # one shape per launch (round 6)                                                                                       # 29: F(3x3, 2x2) for the 4x4 / stride-2 layers (conv_wino_s2.h)
+# kWgradCfg[i].name of csrc/conv_wgrad_plan.h ("?": a retired number)
 WGRAD_CONFIGS = ["wgrad_kernel<1, 1, 9>", "wgrad_kernel<1, 1, 4>", "wgrad_kernel<2, 2, 1>", "wgrad_kernel<1, 1, 8>",
                  "wgrad_kernel<1, 1, 3>", "wgrad_kernel<1, 1, 1>", "wgrad_kernel<2, 2, 3>",
                  "wgrad_row_kernel<3, 3, 1>", "wgrad_row_kernel<3, 3, -1>", "wgrad_row_kernel<1, 1, 1>",
@@ -606,6 +609,22 @@ def _conv_args(x, w, geom, N, Cc, w_sn, w_sc, out, scale=None, bias=None, add1=N
     a.ws, a.ws_bytes = None, 0
     if FLOP_COUNT is not None and count:
         _count("conv_mfma" if (Cc % 32 == 0 and N % 32 == 0) else "conv_valu", 2.0 * geom.B * geom.OH * geom.OW * N * Cc * geom.TH * geom.TW)
+    return a
+
+
+def _wgrad_args(p, q, geom, N, Cc, dw, w_sn, w_sc, db=None, accumulate=0, half=None):
+    """mtd_wgrad_args of one weight gradient, without a workspace.  accumulate: bit 0 adds into dw, bit 1 into db;
+    half = (scale1, scale2, m_first) as in wgrad()."""
+    a = WgradArgs()
+    a.g = geom
+    a.p, a.p_ld, a.N = p.data_ptr(), ld_of(p), N
+    a.q, a.q_ld, a.C = q.data_ptr(), ld_of(q), Cc
+    a.dw, a.w_sn, a.w_sc = dw.data_ptr(), w_sn, w_sc
+    a.db = _ptr(db)
+    a.accumulate = accumulate
+    a.ws, a.ws_bytes = None, 0
+    if half is not None:
+        a.half_scale, a.half_scale2, a.m_first = half[0].data_ptr(), half[1].data_ptr(), int(half[2])
     return a
 
 
@@ -886,7 +905,8 @@ def wgrad_half_ok(geom, N, Cc, m_first):
     if ok is None:
         a = WgradArgs()
         a.g = geom
-        a.p = a.q = a.dw = a.half_scale = a.half_scale2 = 16            # (non-null, aligned placeholders: the query looks at shapes)
+        # (no tensors here, so not _wgrad_args: non-null, aligned placeholders -- the query looks at shapes)
+        a.p = a.q = a.dw = a.half_scale = a.half_scale2 = 16
         a.p_ld, a.N, a.q_ld, a.C, a.w_sn, a.w_sc, a.m_first = N, N, Cc, Cc, Cc * geom.TH * geom.TW, geom.TH * geom.TW, int(m_first)
         ok = bool(_lib.lib().mtd_conv_wgrad_half_scale_ok(C.byref(a)))
         _half_ok_cache[key] = ok
@@ -902,18 +922,9 @@ def wgrad(p, q, geom, N, Cc, dw, w_sn, w_sc, db=None, accumulate=False, accumula
         wgrad(p, q, geom, N, Cc, dw, w_sn, w_sc, db=db, accumulate=accumulate, accumulate_bias=accumulate_bias, defer=defer)
         return rfft_rows(rows[0], rows[1])
     L = _lib.lib()
-    a = WgradArgs()
-    a.g = geom
-    a.p, a.p_ld, a.N = p.data_ptr(), ld_of(p), N
-    a.q, a.q_ld, a.C = q.data_ptr(), ld_of(q), Cc
-    a.dw, a.w_sn, a.w_sc = dw.data_ptr(), w_sn, w_sc
-    a.db = _ptr(db)
     if accumulate_bias is None:
         accumulate_bias = accumulate
-    a.accumulate = (1 if accumulate else 0) | (2 if accumulate_bias else 0)
-    a.ws, a.ws_bytes = None, 0
-    if half is not None:
-        a.half_scale, a.half_scale2, a.m_first = half[0].data_ptr(), half[1].data_ptr(), int(half[2])
+    a = _wgrad_args(p, q, geom, N, Cc, dw, w_sn, w_sc, db, (1 if accumulate else 0) | (2 if accumulate_bias else 0), half)
     if FLOP_COUNT is not None:
         _count_wgrad(geom, N, Cc, L.mtd_conv_wgrad_plan_cfg(C.byref(a)))
     need = L.mtd_conv_wgrad_ws_bytes(C.byref(a))
@@ -957,14 +968,7 @@ def wgrad_pair(p, q, geom, b_first, N, Cc, dw1, dw2, w_sn, w_sc, db=None, accumu
     L = _lib.lib()
     if p_add is not None and (ld_of(p_add) != ld_of(p) or not WGRAD_SUM):
         p, p_add = add(p, p_add), None
-    a = WgradArgs()
-    a.g = geom
-    a.p, a.p_ld, a.N = p.data_ptr(), ld_of(p), N
-    a.q, a.q_ld, a.C = q.data_ptr(), ld_of(q), Cc
-    a.dw, a.w_sn, a.w_sc = dw1.data_ptr(), w_sn, w_sc
-    a.db = _ptr(db)
-    a.accumulate = 2 if accumulate_bias else 0
-    a.ws, a.ws_bytes = None, 0
+    a = _wgrad_args(p, q, geom, N, Cc, dw1, w_sn, w_sc, db, 2 if accumulate_bias else 0)
     need = L.mtd_conv_wgrad_pair_ws_bytes(C.byref(a), b_first)       # 0: this layer's plan has no pair form
     if p_add is not None and (need == 0 or L.mtd_conv_wgrad_pair_ok(C.byref(a), b_first) != 2):
         p, p_add = add(p, p_add), None
@@ -999,12 +1003,7 @@ def conv_wgrad_fusable(conv_call, wgrad_call):
     if not (FUSE_C32_BWD and DEFER_WGRADS and N == 32 and Cc == 32 and not wkw.get("accumulate")):
         return False
     d = _conv_args(*conv_call[0], count=False, **{k: v for k, v in conv_call[1].items() if k != "wino32"})
-    a = WgradArgs()
-    a.g = geom
-    a.p, a.p_ld, a.N = p_.data_ptr(), ld_of(p_), N
-    a.q, a.q_ld, a.C = q_.data_ptr(), ld_of(q_), Cc
-    a.dw, a.w_sn, a.w_sc = dw.data_ptr(), w_sn, w_sc
-    a.db = _ptr(wkw.get("db"))
+    a = _wgrad_args(p_, q_, geom, N, Cc, dw, w_sn, w_sc, wkw.get("db"))
     return bool(_lib.lib().mtd_conv_c32_bwd_ok(C.byref(d), C.byref(a)))
 
 
@@ -1020,15 +1019,7 @@ def conv_wgrad_fused(conv_call, wgrad_call, defer, spec=None):
         return False
     L = _lib.lib()
     d = _conv_args(*conv_call[0], **{k: v for k, v in conv_call[1].items() if k != "wino32"})
-    a = WgradArgs()
-    a.g = geom
-    a.p, a.p_ld, a.N = p_.data_ptr(), ld_of(p_), N
-    a.q, a.q_ld, a.C = q_.data_ptr(), ld_of(q_), Cc
-    a.dw, a.w_sn, a.w_sc = dw.data_ptr(), w_sn, w_sc
-    db = wkw.get("db")
-    a.db = _ptr(db)
-    a.accumulate = 0
-    a.ws, a.ws_bytes = None, 0
+    a = _wgrad_args(p_, q_, geom, N, Cc, dw, w_sn, w_sc, wkw.get("db"))
     # Round 5: a layer WITHOUT a spectral tail whose weight gradient the library plans on the Winograd 32 x 32 kernel (plan 19,
     # csrc/conv_wgrad_wino32.h: 26 instead of 35 us) goes as two launches -- the halo-tile data gradient with all eight waves + that
     # kernel on the side stream: generator leg 5.33 -> 5.21 ms, step -0.04 ... -0.09 ms (profiles/r5_wgrad32_probe.txt)

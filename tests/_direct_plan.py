@@ -163,7 +163,7 @@ def _wide_plan(g, N, C, p_ld, q_ld, wide_aligned):
 
 
 def wgrad_plan(g, N, C, p_ld, q_ld, wide_aligned=True):
-    """mtd_conv_wgrad with min(N, C) == 1: check_wargs (conv_wgrad.hip:1335-1344), then mtd_direct_wgrad_launch
+    """mtd_conv_wgrad with min(N, C) == 1: check_wargs (conv_wgrad_plan.h), then mtd_direct_wgrad_launch
     (conv_direct.hip:917-957).  wide_aligned: is the base of the V-channel operand (q when N == 1, else p) 16-byte aligned."""
     assert N == 1 or C == 1
     T = g.TH * g.TW
@@ -199,7 +199,7 @@ def wgrad_plan(g, N, C, p_ld, q_ld, wide_aligned=True):
 
 
 def wgrad_ws_floats(plan):
-    """wgrad_ws_floats (conv_wgrad.hip:1357-1367) for a plan of wgrad_plan: the slabs and every intermediate reduce stage."""
+    """wgrad_ws_floats (conv_wgrad_plan.h) for a plan of wgrad_plan: the slabs and every intermediate reduce stage."""
     ns, stride = plan["nblk"], plan["slab_stride"]
     total = ns * stride
     while ns > WGRAD_GS:

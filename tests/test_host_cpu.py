@@ -219,7 +219,7 @@ def test_the_switchboard_is_frozen(built_lib, monkeypatch):
         if fn.endswith((".hip", ".h")):
             for ln in open(os.path.join(csrc, fn)).read().splitlines():
                 if re.search(r"(?<![a-z_])getenv\(", ln):
-                    assert fn == "common.h" and "mtd_lab_env" in ln, (fn, ln)
+                    assert fn == "host_util.h" and "mtd_lab_env" in ln, (fn, ln)
     pkg = os.path.join(ROOT, "mtd-gan_amd")
     for dp_, _d, files in os.walk(pkg):
         for fn in files:
