@@ -416,7 +416,7 @@ int c32_bwd_launch(const mtd_conv_args* d, const mtd_wgrad_args* w, const float*
     if (!nslab || !slab_stride || !mtd_conv_c32_bwd_ok(d, w)) return MTD_EINVAL;
     C32BwdParams fp;
     Plan pl{};
-    pl.cfg = 10; pl.splitk = 1; pl.c_per_split = 32;
+    pl.cfg = CK_C32T; pl.splitk = 1; pl.c_per_split = 32;
     int rc = fill_params(d, pl, fp.d);
     if (rc != MTD_OK) return rc;
     WgradParams& p = fp.w;
@@ -452,7 +452,7 @@ int c32_bwd_launch(const mtd_conv_args* d, const mtd_wgrad_args* w, const float*
     fp.specT = specT;
     if (!w->ws || w->ws_bytes < (size_t)grid * (size_t)p.slab_stride * sizeof(float)) return MTD_EWS;
     hipStream_t s = (hipStream_t)stream;
-    const int prof = mtd_prof_begin(0, specT ? 13 : 11, 1, 2ll * p.M, 32, 32, 9, s,
+    const int prof = mtd_prof_begin(0, specT ? CK_C32_BWD_IRFFT : CK_C32_BWD, 1, 2ll * p.M, 32, 32, 9, s,
                                     algorithmic_bytes(d) + 4.0 * ((double)p.M * 32 + (double)p.M * 32 + 9.0 * 32 * 32) +
                                         (specT ? 4.0 * d->g.B * NKW * 4096 : 0.0));
     if (specT) {

@@ -17,9 +17,7 @@
 //
 // Roofline: fp32 MFMA, 64 FLOP/clk/SIMD (157.3 TFLOP/s chip).  Algorithmic flops = 2*M*N*K.
 #include "common.h"
-#ifndef S2DG_PLAN
-#define S2DG_PLAN 1      // round-5 tile rules for the four-class stride-2 data gradients (make_plan)
-#endif
+#include "conv_plan.h"      // the planner: kernel ids, lab switches, domains, make_plan, the route (host arithmetic only)
 #ifdef MTD_LAB
 #define MTD_IGEMM_FIN 1
 #else
@@ -47,7 +45,6 @@ __device__ unsigned long long* mtd_stamp_buf;
 
 namespace {
 
-constexpr int KC = 32;      // channels per K chunk
 constexpr int BLD = 36;     // LDS row stride of the weight tile (floats): 16-B aligned, conflict-free b128
 
 struct IgemmParams {
@@ -744,7 +741,6 @@ __global__ __launch_bounds__(256, (WM * WN >= 4) ? 2 : 1) void igemm_kernel(cons
 // Each set has its own geometry offsets, operands and outputs -- the four input-parity classes of a stride-2 data
 // gradient (each a 2x2-tap stride-1 gather writing every other output pixel), which as four launches of 27-35 us ran at
 // 60-79 TFLOP/s, half of them split-K with an epilogue launch each.
-constexpr int MULTI_MAX = 4;
 struct IgemmMulti { IgemmParams p[MULTI_MAX]; };
 
 template <int WM, int WN, int WGM, int WGN>
@@ -768,7 +764,6 @@ __global__ __launch_bounds__(256, (WM * WN >= 4) ? 2 : 1) void igemm_multi_kerne
 // barrier covers ALL taps of one 32-channel chunk ([tap][32 n][32 c], <= 9 taps = 41 KB) instead of one tap: two
 // workgroup barriers per 9 x 16 MFMAs instead of nine, none at all inside a chunk, so the four waves drift freely
 // and the next chunk's weights (9 x 16 bytes per thread) are in flight during the whole chunk.  Tile 128*WM x 32.
-constexpr int TB_MAXT = 9;
 
 template <int WM>
 __global__ __launch_bounds__(256, 2) void igemm_tb_kernel(const IgemmParams p) {
@@ -1057,7 +1052,7 @@ __global__ __launch_bounds__(256, 2) void igemm_c32p_kernel(const IgemmParams p,
 // operands are requested before the MFMA loop and waited for after it, and the output stores drain under the next
 // tile's MFMAs, so memory phases and MFMA phases of a CU overlap instead of alternating chip-wide.
 // LDS: 2 x 50 KB tiles + 36 KB weights.
-constexpr int C32T_W = 64, C32T_R = 4, C32T_HW = C32T_W + 2;
+constexpr int C32T_HW = C32T_W + 2;
 
 // R image rows per tile, 2 R waves per workgroup.  DB: two halo buffers, one workgroup per CU, the next tile's DMA under this
 // tile's MFMAs (R = 4).  !DB (R = 2, lab variant MTD_C32T_VARIANT=1): one halo buffer of half the size, TWO workgroups per CU
@@ -1255,31 +1250,6 @@ __global__ __launch_bounds__(128 * R, DB ? 1 : 2) void igemm_c32t_kernel(const I
     }
 }
 
-// 16-byte epilogue vectors (EpiWide): every operand row 16-byte aligned
-bool wide_epilogue_ok(const mtd_conv_args& a) {
-    if (!aligned16(a.out) || (a.out_ld % 4)) return false;
-    if (a.bias && !aligned16(a.bias)) return false;
-    if (a.add1 && (!aligned16(a.add1) || (a.add1_ld % 4))) return false;
-    if (a.add2 && (!aligned16(a.add2) || (a.add2_ld % 4))) return false;
-    if (a.mask && (!aligned16(a.mask) || (a.mask_ld % 4))) return false;
-    if (a.out2 && (!aligned16(a.out2) || (a.out2_ld % 4))) return false;
-    return true;
-}
-
-// the halo-tile kernel's geometry: 3x3, stride 1, every tap within one pixel of the output position, 64-pixel rows
-bool c32t_eligible(const mtd_conv_args& a) {
-    const mtd_geom& g = a.g;
-    if (a.C != 32 || g.TH != 3 || g.TW != 3 || g.in_sy != 1 || g.in_sx != 1) return false;
-    if (g.OW != C32T_W || g.IW != C32T_W || g.IH != g.OH || (g.OH % C32T_R)) return false;
-    if (!(g.out_sy == 1 && g.out_sx == 1 && g.out_oy == 0 && g.out_ox == 0 && g.OHF == g.OH && g.OWF == g.OW)) return false;
-    for (int i = 0; i < 3; ++i) {
-        const int dy = g.off_y + i * g.tap_dy, dx = g.off_x + i * g.tap_dx;
-        if (dy < -1 || dy > 1 || dx < -1 || dx > 1) return false;
-    }
-    return true;
-}
-
-
 // ---- v2: 128 x 128 workgroup tile, both operands through LDS by LDS-DMA ---------------------------------------------
 // The 3x3 layers are bound by L2 bandwidth in the kernels above: every 32-wide n-tile re-reads its activation tile for
 // each of the nine taps (measured: the generator conv's loads alone take 20 us = 7.4 TB/s of L2 traffic).  Here one
@@ -1437,152 +1407,8 @@ __device__ __forceinline__ void splitk_epilogue_body(const IgemmParams& p) {
 __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const IgemmParams p) { splitk_epilogue_body(p); }
 __global__ __launch_bounds__(256) void splitk_epilogue_multi_kernel(const IgemmMulti mp) { splitk_epilogue_body(mp.p[blockIdx.y]); }
 
-bool splitk_vec_ok(const mtd_conv_args& a, long long M) {
-    if (M * a.N >= (1ll << 31) || !aligned16(a.ws) || !aligned16(a.out) || (a.out_ld % 4)) return false;
-    if (a.bias && !aligned16(a.bias)) return false;
-    if (a.add1 && (!aligned16(a.add1) || (a.add1_ld % 4))) return false;
-    if (a.add2 && (!aligned16(a.add2) || (a.add2_ld % 4))) return false;
-    if (a.mask && (!aligned16(a.mask) || (a.mask_ld % 4))) return false;
-    return true;
-}
-
-struct Plan { int cfg, BM, BN, splitk, c_per_split; };
-
-int g_force_cfg = -1, g_force_split = -1;      // tuning hook (mtd_conv_igemm_override)
-constexpr int NCFG = 9;
-const int kCfgBM[NCFG] = {256, 128, 256, 64, 128, 32, 128, 256, 128};
-const int kCfgBN[NCFG] = {32, 32, 64, 64, 128, 128, 32, 32, 128};
-
-Plan make_plan(const mtd_conv_args& a, int sets = 1) {
-    const long long M = geom_pixels(a.g) * sets;        // tile choice by the pixels of the whole grid (all sets)
-    Plan pl{};
-    if (g_force_cfg >= 0 && g_force_cfg < NCFG && a.N % kCfgBN[g_force_cfg] == 0 && (g_force_cfg < 6 || g_force_cfg == 8 || a.g.TH * a.g.TW <= TB_MAXT)) {
-        pl.cfg = g_force_cfg; pl.BM = kCfgBM[pl.cfg]; pl.BN = kCfgBN[pl.cfg];
-        int chunks = a.C / KC;
-        int sk = g_force_split > 0 ? g_force_split : 1;
-        if (sk > chunks) sk = chunks;
-        int cps = (chunks + sk - 1) / sk;
-        pl.splitk = (chunks + cps - 1) / cps;
-        pl.c_per_split = cps * KC;
-        return pl;
-    }
-    // Derived from the standalone sweep of all 109 conv shapes of the training step (tools/tune_igemm.py, profiles/):
-    // fp32 MFMA is slow enough (64 clk per 32x32x2) that one 32x32 accumulator tile per wave at high occupancy beats the
-    // register-blocked tiles almost everywhere; the wide tiles only pay for the huge-M, thin-K first-stage layers.
-    pl.cfg = 1;
-    if ((M >= 131072 && a.N >= 64) || (M >= 32768 && a.N >= 256 && a.C <= 64) || (M >= 65536 && a.N >= 128) ||
-        (M >= 16384 && a.N >= 512 && a.C <= 128)) pl.cfg = 0;
-    else if (M >= 32768 && a.N == 64 && a.C >= 128) pl.cfg = 3;
-    // tap-block kernel (all taps of a channel chunk per barrier; 41 KB of LDS = 3 workgroups per CU): 5-9 % faster on the
-    // paired-pass shapes (profiles/r1_igemm_tile_sweep.txt) when several chunks stream and the grid fits one round of residency
-    if (pl.cfg == 1 && a.C >= 128 && M >= 4096 && a.g.TH * a.g.TW == TB_MAXT) {        // (1x1 layers: 30-40 % slower there)
-        const long long b6 = ((M + 127) / 128) * (a.N / 32);
-        const long long sk6 = b6 <= 256 ? 512 / b6 : 1;
-        if (b6 * sk6 <= 768) pl.cfg = 6;
-    }
-    // Round 2, after the transposed accumulator blocks (the 256 x 64 tile lost its scratch spill and both tap-block forms their
-    // dword epilogues): the standalone sweep of the step's 98 shapes (profiles/r2_igemm_tile_sweep.txt) puts the 256 x 64 tile
-    // 5-9 % ahead on every large 3x3 grid, 1.25 ms per step over all shapes.  INSIDE the step the rules below (MTD_IGEMM_PLAN=2)
-    // move 7.0 ms of launches onto that tile and 1.6 ms onto the two-block tap-block kernel and the family's total does not
-    // change (20.63 -> 20.58 ms in the one-stream trace, step 40.26 vs 40.40 ms): standalone timings on repeated launches
-    // do not predict the in-step ranking at this margin.  Off by default.
-    static const int env_plan = [] { const char* e = mtd_lab_env("MTD_IGEMM_PLAN"); return e ? atoi(e) : 1; }();
-    const int T9 = a.g.TH * a.g.TW == TB_MAXT;
-    if (env_plan >= 2 && sets == 1 && T9) {
-        const long long MN = M * a.N;
-        if ((a.N % 64) == 0 && a.C >= 64 && MN >= (4ll << 20) && !(M >= 65536 && a.N >= 256 && a.C <= 64)) {
-            pl.cfg = 2;         // 256 x 64, four blocks per wave: 5-9 % over the 128 / 256 x 32 tiles on every grid this large
-        } else if (a.C >= 128 && MN >= (2ll << 20) && MN < (4ll << 20) && (M / 256) * (a.N / 32) >= 256 && a.N <= 256) {
-            pl.cfg = 7;         // tap-block kernel with two blocks per wave: 16384 x 128, 32768 x 64, 8192 x 256
-        }
-    }
-    // Round 5: the four-class stride-2 data gradients (sets == 4, 2 x 2 taps) had kept round 2's tiles; re-timed on the step's shapes
-    // (tools/s2_dgrad_probe.py, us per launch, plan -> new): 65536 x 4 pixels, 64 channels 119 -> 108 (256 x 64 tile); 16384 x 4, 128:
-    // 90 -> 87; 4096 x 4, 256: 95 -> 79 (256 x 32); the G step's unpaired passes 32768 x 4, 64: 61 -> 57; 8192 x 4, 128: 58 -> 48;
-    // 2048 x 4, 256: 60 -> 44 (128 x 32 WITHOUT the split of K).  The 512-channel levels keep the plan.
-    bool unsplit = false;
-    if (S2DG_PLAN && sets == 4 && a.g.TH * a.g.TW == 4) {
-        if ((a.N == 64 && M >= 131072) || (a.N == 128 && M >= 32768)) { pl.cfg = 2; unsplit = true; }
-        else if (a.N == 256 && M >= 16384) { pl.cfg = 0; unsplit = true; }
-        else if (a.N == 256 && M >= 8192) { pl.cfg = 1; unsplit = true; }
-    }
-    // ... and the first 4 x 4 stride-2 forward conv (down1: 64 -> 64 channels; tools/s2_fwd_probe.py): 65536 pixels 99 -> 82 us on the
-    // 256 x 64 tile, the G step's 32768 pixels 64 -> 45 on the 64 x 64 tile, both unsplit; the deeper levels keep the plan (it is the best there)
-    if (S2DG_PLAN && sets == 1 && a.g.TH * a.g.TW == 16 && a.N == 64 && a.C == 64) {
-        if (M >= 65536) { pl.cfg = 2; unsplit = true; }
-        else if (M >= 32768) { pl.cfg = 3; unsplit = true; }
-    }
-    pl.BM = kCfgBM[pl.cfg];
-    pl.BN = kCfgBN[pl.cfg];
-    const long long Mset = geom_pixels(a.g);
-    long long blocks = ((Mset + pl.BM - 1) / pl.BM) * (a.N / pl.BN) * sets;
-    int chunks = a.C / KC;
-    int sk = blocks <= 256 ? (int)(512 / blocks) : 1;      // fill ~2 workgroups per CU; never split a grid that already does
-    if (blocks > 256 && blocks <= 512 && chunks * a.g.TH * a.g.TW <= 32) sk = 2;      // ... unless its workgroups are short (2x2-tap data gradients: -22 %)
-    if (env_plan >= 2 && sets == 1 && T9 && blocks == 256) {
-        // a grid of exactly one workgroup per CU: the register-blocked tiles do not want the split at all, the tap-block
-        // kernel only when its K loop is long (4096 x 256 x 256: 45 us unsplit, 51 split; 2048 x 512 x 512: 91 / 87)
-        if (pl.cfg == 2 || pl.cfg == 7) sk = 1;
-        else if (pl.cfg == 6 && (long long)a.C * 9 < 4096) sk = 1;
-    }
-    if (unsplit) sk = 1;
-    if (sk > chunks) sk = chunks;
-    if (sk > 32) sk = 32;
-    if (sk < 1) sk = 1;
-    int cps = ((chunks + sk - 1) / sk);
-    sk = (chunks + cps - 1) / cps;
-    pl.splitk = sk;
-    pl.c_per_split = cps * KC;
-    return pl;
-}
-
-int check_args(const mtd_conv_args& a) {
-    if (!a.in || !a.w || !a.out) return MTD_EINVAL;
-    if (a.C <= 0 || a.N <= 0 || (a.C % 32) || (a.N % 32)) return MTD_EINVAL;
-    const mtd_geom& g = a.g;
-    if (g.B <= 0 || g.IH <= 0 || g.IW <= 0 || g.OH <= 0 || g.OW <= 0) return MTD_EINVAL;
-    if (g.TH <= 0 || g.TW <= 0 || g.TH * g.TW > 16) return MTD_EINVAL;
-    if (geom_pixels(g) > (1ll << 30)) return MTD_EINVAL;
-    if (a.in_ld < a.C || a.out_ld < a.N || (a.in_ld % 4)) return MTD_EINVAL;
-    if (!aligned16(a.in)) return MTD_EALIGN;
-    if (a.w_sc != 1 || a.w_st < 0) return MTD_EINVAL;                     // packed / natively c-contiguous weight view
-    if (!aligned16(a.w) || (a.w_sn % 4) || (a.g.TH * a.g.TW > 1 && (a.w_st % 4))) return MTD_EALIGN;
-    if (a.add1 && a.add1_ld < a.N) return MTD_EINVAL;
-    if (a.add2 && a.add2_ld < a.N) return MTD_EINVAL;
-    if (a.mask && a.mask_ld < a.N) return MTD_EINVAL;
-    if (a.out2 && a.out2_ld < a.N) return MTD_EINVAL;
-    // the furthest output pixel must stay inside the OHF x OWF image
-    if ((g.OH - 1) * g.out_sy + g.out_oy >= g.OHF || (g.OW - 1) * g.out_sx + g.out_ox >= g.OWF) return MTD_EINVAL;
-    return MTD_OK;
-}
-
-}  // namespace
-
-#ifndef MTD_NO_API      // (conv_c32_bwd.hip includes this file for its kernels and helpers only)
-extern "C" int mtd_conv_igemm_override(int cfg, int splitk) {
-    g_force_cfg = cfg;
-    g_force_split = splitk;
-    return MTD_OK;
-}
-
-// Does mtd_conv_igemm take these arguments with act = MTD_ACT_RELU_ADD?  (The persistent kernel of the generator-shaped layers:
-// its two epilogue forms implement it; no split-K, no mask, no second output.)
-extern "C" int mtd_conv_relu_add_ok(const mtd_conv_args* a) {
-    if (!a || check_args(*a) != MTD_OK || a->out2 || a->mask) return 0;
-    const bool gen_shape = a->C == 32 && a->g.TH * a->g.TW == 9 && geom_pixels(a->g) >= 32768;
-    return (g_force_cfg == -1 || g_force_cfg == 9) && gen_shape ? 1 : 0;
-}
-
-extern "C" size_t mtd_conv_igemm_ws_bytes(const mtd_conv_args* a) {
-    if (!a || check_args(*a) != MTD_OK) return 0;
-    Plan pl = make_plan(*a);
-    if (pl.splitk <= 1) return 0;
-    return (size_t)pl.splitk * (size_t)geom_pixels(a->g) * a->N * sizeof(float);
-}
-
-#endif  // MTD_NO_API
-
-namespace {
+// ---- host side: the parameter fill, the split-K finish, the dispatch and the C API.  The planner -- kernel ids, domains,
+// make_plan, the route -- is conv_plan.h.
 
 // everything of IgemmParams that follows from the arguments and the plan
 int fill_params(const mtd_conv_args* a, const Plan& pl, IgemmParams& p) {
@@ -1613,24 +1439,15 @@ int fill_params(const mtd_conv_args* a, const Plan& pl, IgemmParams& p) {
         const long long wb = ((long long)(a->N - 1) * a->w_sn + (long long)kmax * a->w_st + a->C) * 4;
         p.w_bytes = wb >= (1ll << 31) ? 0x7FFFFFFFu : (unsigned)wb;
     }
-    const mtd_geom& g = a->g;
-    p.out_identity = (g.out_sy == 1 && g.out_sx == 1 && g.out_oy == 0 && g.out_ox == 0 && g.OHF == g.OH && g.OWF == g.OW);
-    p.out_linear = p.out_identity || (g.OW % 32 == 0);
-    static const int env_xcd = [] { const char* e = mtd_lab_env("MTD_IGEMM_XCD"); return e ? atoi(e) : 1; }();
-    p.xcd_map = env_xcd;
-    static const int env_nt = [] { const char* e = mtd_lab_env("MTD_IGEMM_NT"); return e ? atoi(e) : 0; }();
-    p.nt_store = env_nt;
-    p.wide = (wide_epilogue_ok(*a) ? 1 : 0) | ((pl.splitk > 1 && aligned16(a->ws)) ? 2 : 0);
+    p.out_identity = out_identity(a->g);
+    p.out_linear = out_linear(a->g);
+    p.xcd_map = conv_lab().igemm_xcd;
+    p.nt_store = conv_lab().igemm_nt;
+    p.wide = conv_wide(a, 1, pl.splitk);
     p.fin = 0;
     if (pl.splitk > 1) {
-        size_t need = (size_t)pl.splitk * (size_t)p.M * a->N * sizeof(float);
-        if (!a->ws || a->ws_bytes < need) return MTD_EWS;
-        // finish inside the kernel when the caller brought arrival counters for every output tile (MTD_SPLITK_FIN=0: lab
-        // switch back to the separate epilogue launch)
-        static const int env_fin = [] { const char* e = mtd_lab_env("MTD_SPLITK_FIN"); return e ? atoi(e) : 1; }();
-        const long long tiles = (long long)((p.M + pl.BM - 1) / pl.BM) * (a->N / pl.BN);
-        static const int env_fin_max = [] { const char* e = mtd_lab_env("MTD_SPLITK_FIN_MAX"); return e ? atoi(e) : 8; }();
-        p.fin = (MTD_IGEMM_FIN && env_fin && pl.cfg != 7 && a->tile_ctr && tiles <= (long long)a->tile_ctr_len && pl.splitk <= env_fin_max) ? (splitk_vec_ok(*a, p.M) ? 1 : 2) : 0;
+        if (!a->ws || a->ws_bytes < splitk_ws_bytes(*a, pl.splitk)) return MTD_EWS;
+        p.fin = conv_fin(*a, pl);
     }
     return MTD_OK;
 }
@@ -1641,77 +1458,133 @@ double algorithmic_bytes(const mtd_conv_args* a) {
                   (double)geom_pixels(a->g) * a->N * (1 + (a->add1 != nullptr) + (a->add2 != nullptr) + (a->mask != nullptr) + (a->out2 != nullptr)));
 }
 
+// The launch that sums the split-K slabs of p[0 .. count), problems of one shape, and runs their epilogues: four values per
+// thread where a problem's operands allow it (splitk_vec_ok), value by value otherwise, at most 2048 workgroups.  grouped: ONE
+// launch for all problems when every one of them takes the 16-byte form, else one value-by-value launch each; not grouped: one
+// launch per problem in the form it takes.
+int launch_splitk_finish(const IgemmParams* p, int count, bool grouped, hipStream_t s) {
+    const long long total = (long long)p[0].M * p[0].a.N;
+    const auto blocks_of = [total](bool vec) {
+        const long long blocks = ((vec ? total / 4 : total) + 255) / 256;
+        return (int)(blocks > 2048 ? 2048 : blocks);
+    };
+    bool all_vec = true;
+    for (int i = 0; i < count; ++i) all_vec = all_vec && splitk_vec_ok(p[i].a, p[i].M);
+    if (grouped && all_vec) {
+        IgemmMulti mp;
+        for (int i = 0; i < MULTI_MAX; ++i) mp.p[i] = p[i < count ? i : 0];      // (rows of the grid: blockIdx.y < count)
+        hipLaunchKernelGGL(splitk_epilogue_multi_kernel, dim3(blocks_of(true), count), dim3(256), 0, s, mp);
+        MTD_LAUNCH_CHECK();
+        return MTD_OK;
+    }
+    for (int i = 0; i < count; ++i) {
+        const bool vec = !grouped && splitk_vec_ok(p[i].a, p[i].M);
+        if (vec) hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks_of(true)), dim3(256), 0, s, p[i]);
+        else hipLaunchKernelGGL(splitk_epilogue_scalar_kernel, dim3(blocks_of(false)), dim3(256), 0, s, p[i]);
+        MTD_LAUNCH_CHECK();
+    }
+    return MTD_OK;
+}
+
 }  // namespace
 
-#ifndef MTD_NO_API
+#ifndef MTD_NO_API      // (conv_winograd.hip and conv_c32_bwd.hip include this file for its kernels and helpers only)
+namespace {
+
+// The tile-shape switch, once: the cases of FAMILY (CK_IGEMM: KERNEL = igemm_kernel; CK_MULTI: igemm_multi_kernel).  SINGLE_ONLY:
+// the cases of the tile kernels without a multi form; they stand before the last tile shape so that every kernel template is
+// first used where it always was -- that order is the order of the kernels in the code object.
+#define IGEMM_TILE_CASES(FAMILY, KERNEL, SINGLE_ONLY, ARG)                                            \
+    case FAMILY##_256x32: MTD_LAUNCH((KERNEL<2, 1, 4, 1>), tile_grid, dim3(256), 0, s, ARG); break;   \
+    case FAMILY##_128x32: MTD_LAUNCH((KERNEL<1, 1, 4, 1>), tile_grid, dim3(256), 0, s, ARG); break;   \
+    case FAMILY##_256x64: MTD_LAUNCH((KERNEL<2, 2, 4, 1>), tile_grid, dim3(256), 0, s, ARG); break;   \
+    case FAMILY##_64x64: MTD_LAUNCH((KERNEL<1, 1, 2, 2>), tile_grid, dim3(256), 0, s, ARG); break;    \
+    case FAMILY##_128x128: MTD_LAUNCH((KERNEL<2, 2, 2, 2>), tile_grid, dim3(256), 0, s, ARG); break;  \
+    SINGLE_ONLY                                                                                       \
+    case FAMILY##_32x128: MTD_LAUNCH((KERNEL<1, 1, 1, 4>), tile_grid, dim3(256), 0, s, ARG); break;
+
+// The dispatch: ONE launch of kernel k.  p: the launch parameters -- of set 0 of a multi form, whose `count` sets are mp;
+// pl: the tile plan (tile kernels); T: the spectrum of CK_C32T_TAIL.
+void igemm_dispatch(int k, const Plan& pl, const IgemmParams& p, const IgemmMulti* mp, int count, const float* T, hipStream_t s) {
+    const ConvLab& lab = conv_lab();
+    const mtd_conv_args& a = p.a;
+    const dim3 tile_grid((p.M + pl.BM - 1) / pl.BM, a.N / pl.BN, pl.splitk * count);
+    const int halo_tiles = p.M / (C32T_R * C32T_W);
+    const int halo_wgs = halo_tiles < 256 ? halo_tiles : 256;
+    switch (k) {
+        case CK_C32T:       // generator-shaped layers on 64-pixel rows: halo tiles of four image rows, one persistent workgroup per CU
+            if (lab.c32t_variant == 1) {
+                const int ntiles = p.M / (2 * C32T_W);
+                MTD_LAUNCH((igemm_c32t_kernel<2, false>), dim3(ntiles < 512 ? ntiles : 512, a.N / 32), dim3(256), 0, s, p, ntiles, lab.c32t_stagger, (const float*)nullptr);
+            } else if (lab.c32t_wide && wide_epilogue_ok(a)) {
+                MTD_LAUNCH((igemm_c32t_kernel<C32T_R, true, true>), dim3(halo_wgs, a.N / 32), dim3(512), 0, s, p, halo_tiles, 0, (const float*)nullptr);
+            } else {
+                MTD_LAUNCH((igemm_c32t_kernel<C32T_R, true>), dim3(halo_wgs, a.N / 32), dim3(512), 0, s, p, halo_tiles, 0, (const float*)nullptr);
+            }
+            break;
+        case CK_C32P: {     // generator-shaped layers: persistent kernel, two 32-pixel tiles per wave at M = 131072
+            const int ntiles = (p.M + 31) / 32;
+            const int wgs = (ntiles + 7) / 8;
+            MTD_LAUNCH(igemm_c32p_kernel, dim3(wgs < 512 ? wgs : 512, a.N / 32), dim3(256), 0, s, p, ntiles);
+            break;
+        }
+        IGEMM_TILE_CASES(CK_IGEMM, igemm_kernel,
+                         case CK_TB_128x32: MTD_LAUNCH((igemm_tb_kernel<1>), tile_grid, dim3(256), 0, s, p); break;
+                         case CK_TB_256x32: MTD_LAUNCH((igemm_tb_kernel<2>), tile_grid, dim3(256), 0, s, p); break;
+                         case CK_V2_128x128: MTD_LAUNCH((igemm_v2_kernel<0>), tile_grid, dim3(256), 0, s, p); break;, p)
+        case CK_C32T_TAIL: {
+#ifdef MTD_LAB       // lab builds only (stage switches that produce WRONG results); never read from the environment by the shipped library
+            const int tail_lab = lab.tail_lab;
+#else
+            const int tail_lab = 0;
+#endif
+            MTD_LAUNCH((igemm_c32t_kernel<C32T_R, true, true, true>), dim3(halo_wgs, 1), dim3(512), 0, s, p, halo_tiles, tail_lab, T);
+            break;
+        }
+        // (split-K sets finish through splitk_epilogue_multi_kernel: with the in-kernel finish inlined four times the compiler
+        // merges the tails and selects the argument set dynamically -- 2.4 KB of scratch per lane)
+        IGEMM_TILE_CASES(CK_MULTI, igemm_multi_kernel, , *mp)
+        default: break;     // (no other kernel of the family is launched from this file)
+    }
+}
+#undef IGEMM_TILE_CASES
+
+ConvForce g_igemm_force;      // tuning hook (mtd_conv_igemm_override): cfg and split
+
+}  // namespace
+
+extern "C" int mtd_conv_igemm_override(int cfg, int splitk) {
+    g_igemm_force.cfg = cfg;
+    g_igemm_force.split = splitk;
+    return MTD_OK;
+}
+
+// Does mtd_conv_igemm take these arguments with act = MTD_ACT_RELU_ADD?  (The persistent kernel of the generator-shaped layers:
+// its two epilogue forms implement it; no split-K, no mask, no second output.)
+extern "C" int mtd_conv_relu_add_ok(const mtd_conv_args* a) {
+    return a && check_args(*a) == MTD_OK && conv_relu_add_ok(*a, g_igemm_force) ? 1 : 0;
+}
+
+extern "C" size_t mtd_conv_igemm_ws_bytes(const mtd_conv_args* a) {
+    if (!a || check_args(*a) != MTD_OK) return 0;
+    return splitk_ws_bytes(*a, make_plan(*a, g_igemm_force).splitk);
+}
+
 extern "C" int mtd_conv_igemm(const mtd_conv_args* a, void* stream) {
     if (!a) return MTD_EINVAL;
     int rc = check_args(*a);
     if (rc != MTD_OK) return rc;
-    Plan pl = make_plan(*a);
+    const ConvRoute r = conv_igemm_route(*a, 1, g_igemm_force);
     IgemmParams p;
-    rc = fill_params(a, pl, p);
+    rc = fill_params(a, r.plan, p);
     if (rc != MTD_OK) return rc;
+    if (r.kernel < 0) return r.kernel;
     hipStream_t s = (hipStream_t)stream;
-    const double alg_bytes = algorithmic_bytes(a);      // profiler record
-    const bool gen_shape = a->C == 32 && a->g.TH * a->g.TW == 9 && p.M >= 32768;
-    if ((g_force_cfg == -1 || g_force_cfg == 10) && gen_shape && c32t_eligible(*a) && a->act != MTD_ACT_RELU_ADD) {
-        // generator-shaped layers on 64-pixel rows: halo tiles of four image rows, one persistent workgroup per CU
-        const int prof = mtd_prof_begin(0, 10, 1, p.M, a->N, a->C, 9, s, alg_bytes);
-        static const int env_variant = [] { const char* e = mtd_lab_env("MTD_C32T_VARIANT"); return e ? atoi(e) : 0; }();
-        static const int env_stagger = [] { const char* e = mtd_lab_env("MTD_C32T_STAGGER"); return e ? atoi(e) : 0; }();
-        if (env_variant == 1) {
-            const int ntiles = p.M / (2 * C32T_W);
-            MTD_LAUNCH((igemm_c32t_kernel<2, false>), dim3(ntiles < 512 ? ntiles : 512, a->N / 32), dim3(256), 0, s, p, ntiles, env_stagger, (const float*)nullptr);
-        } else {
-            const int ntiles = p.M / (C32T_R * C32T_W);
-            static const int env_wide = [] { const char* e = mtd_lab_env("MTD_C32T_WIDE"); return e ? atoi(e) : 1; }();
-            if (env_wide && wide_epilogue_ok(*a))
-                MTD_LAUNCH((igemm_c32t_kernel<C32T_R, true, true>), dim3(ntiles < 256 ? ntiles : 256, a->N / 32), dim3(512), 0, s, p, ntiles, 0, (const float*)nullptr);
-            else
-            MTD_LAUNCH((igemm_c32t_kernel<C32T_R, true>), dim3(ntiles < 256 ? ntiles : 256, a->N / 32), dim3(512), 0, s, p, ntiles, 0, (const float*)nullptr);
-        }
-        mtd_prof_end(prof, s);
-        MTD_LAUNCH_CHECK();
-        return MTD_OK;
-    }
-    if (a->out2) return MTD_EINVAL;               // second output: halo-tile kernel only
-    if (a->act == MTD_ACT_RELU_ADD && !((g_force_cfg == -1 || g_force_cfg == 9) && gen_shape && !a->mask)) return MTD_EINVAL;
-    if ((g_force_cfg == -1 || g_force_cfg == 9) && gen_shape) {
-        // generator-shaped layers: persistent kernel, two 32-pixel tiles per wave at M = 131072
-        const int ntiles = (p.M + 31) / 32;
-        int wgs = (ntiles + 7) / 8;
-        if (wgs > 512) wgs = 512;
-        const int prof = mtd_prof_begin(0, 9, 1, p.M, a->N, a->C, 9, s, alg_bytes);
-        MTD_LAUNCH(igemm_c32p_kernel, dim3(wgs, a->N / 32), dim3(256), 0, s, p, ntiles);
-        mtd_prof_end(prof, s);
-        MTD_LAUNCH_CHECK();
-        return MTD_OK;
-    }
-    dim3 grid((p.M + pl.BM - 1) / pl.BM, a->N / pl.BN, pl.splitk);
-    const int prof = mtd_prof_begin(0, pl.cfg, pl.splitk, p.M, a->N, a->C, a->g.TH * a->g.TW, s, alg_bytes);
-    switch (pl.cfg) {
-        case 0: MTD_LAUNCH((igemm_kernel<2, 1, 4, 1>), grid, dim3(256), 0, s, p); break;
-        case 1: MTD_LAUNCH((igemm_kernel<1, 1, 4, 1>), grid, dim3(256), 0, s, p); break;
-        case 2: MTD_LAUNCH((igemm_kernel<2, 2, 4, 1>), grid, dim3(256), 0, s, p); break;
-        case 3: MTD_LAUNCH((igemm_kernel<1, 1, 2, 2>), grid, dim3(256), 0, s, p); break;
-        case 4: MTD_LAUNCH((igemm_kernel<2, 2, 2, 2>), grid, dim3(256), 0, s, p); break;
-        case 6: MTD_LAUNCH((igemm_tb_kernel<1>), grid, dim3(256), 0, s, p); break;
-        case 7: MTD_LAUNCH((igemm_tb_kernel<2>), grid, dim3(256), 0, s, p); break;
-        case 8: MTD_LAUNCH((igemm_v2_kernel<0>), grid, dim3(256), 0, s, p); break;
-        default: MTD_LAUNCH((igemm_kernel<1, 1, 1, 4>), grid, dim3(256), 0, s, p); break;
-    }
+    const int prof = mtd_prof_begin(0, r.kernel, r.plan.splitk, p.M, a->N, a->C, conv_taps(*a), s, algorithmic_bytes(a));
+    igemm_dispatch(r.kernel, r.plan, p, nullptr, 1, nullptr, s);
     mtd_prof_end(prof, s);
     MTD_LAUNCH_CHECK();
-    if (pl.splitk > 1 && !p.fin) {
-        const long long total = (long long)p.M * a->N;
-        const bool vec = splitk_vec_ok(*a, p.M);
-        int blocks = (int)(((vec ? total / 4 : total) + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        if (vec) hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(splitk_epilogue_scalar_kernel, dim3(blocks), dim3(256), 0, s, p);
-        MTD_LAUNCH_CHECK();
-    }
+    if (r.plan.splitk > 1 && !p.fin) return launch_splitk_finish(&p, 1, false, s);
     return MTD_OK;
 }
 
@@ -1722,30 +1595,20 @@ extern "C" int mtd_conv_igemm(const mtd_conv_args* a, void* stream) {
 // re-reads of `in` and `out2`.  Halo-tile kernel only: C = N = 32, 3x3 stride 1 "same", 64-pixel rows, >= 32768 pixels, no
 // add / mask operands, a->out2 may be NULL.  MTD_EINVAL otherwise (the caller then issues the two launches).
 extern "C" int mtd_resfft_block_tail_ok(const mtd_conv_args* a) {
-    if (!a || check_args(*a) != MTD_OK) return 0;
-    if (a->N != 32 || a->C != 32 || a->g.TH * a->g.TW != 9 || geom_pixels(a->g) < 32768 || !c32t_eligible(*a)) return 0;
-    if (a->add1 || a->add2 || a->mask || a->scale2 || !wide_epilogue_ok(*a)) return 0;
-    if (a->g.OH != 64) return 0;                     // T is the spectrum of 64 x 64 patches
-    return 1;
+    return a && check_args(*a) == MTD_OK && c32t_tail_ok(*a) ? 1 : 0;      // (T is the spectrum of 64 x 64 patches)
 }
 
 extern "C" int mtd_resfft_block_tail(const mtd_conv_args* a, const float* T, void* stream) {
     if (!a || !T || !mtd_resfft_block_tail_ok(a)) return MTD_EINVAL;
     if (!aligned16(T)) return MTD_EALIGN;
-    Plan pl = make_plan(*a);
+    const Plan pl = make_plan(*a, g_igemm_force);
     IgemmParams p;
     int rc = fill_params(a, pl, p);
     if (rc != MTD_OK) return rc;
     if ((long long)a->g.B * NKW * 4096 * 4 >= (1ll << 31)) return MTD_EINVAL;      // 32-bit offsets into T
     hipStream_t s = (hipStream_t)stream;
-    const int ntiles = p.M / (C32T_R * C32T_W);
-    const int prof = mtd_prof_begin(0, 12, 1, p.M, a->N, a->C, 9, s, algorithmic_bytes(a) + 4.0 * a->g.B * NKW * 4096);
-#ifdef MTD_LAB       // lab builds only (stage switches that produce WRONG results); never read from the environment by the shipped library
-    static const int env_lab = [] { const char* e = mtd_lab_env("MTD_TAIL_LAB"); return e ? atoi(e) : 0; }();
-#else
-    const int env_lab = 0;
-#endif
-    MTD_LAUNCH((igemm_c32t_kernel<C32T_R, true, true, true>), dim3(ntiles < 256 ? ntiles : 256, 1), dim3(512), 0, s, p, ntiles, env_lab, T);
+    const int prof = mtd_prof_begin(0, CK_C32T_TAIL, 1, p.M, a->N, a->C, 9, s, algorithmic_bytes(a) + 4.0 * a->g.B * NKW * 4096);
+    igemm_dispatch(CK_C32T_TAIL, pl, p, nullptr, 1, T, s);
     mtd_prof_end(prof, s);
     MTD_LAUNCH_CHECK();
     return MTD_OK;
@@ -1753,21 +1616,12 @@ extern "C" int mtd_resfft_block_tail(const mtd_conv_args* a, const float* T, voi
 
 // Up to four launches of one shape as ONE grid (igemm_multi_kernel).  a[0..count): identical M, N, C, taps, weight view
 // strides and epilogue operand KINDS (each set brings its own pointers / geometry offsets); every set with split-K needs
-// its own workspace of mtd_conv_igemm_multi_ws_bytes(a, count) bytes.  Falls back to `count` single launches when the
-// plan picks a kernel without a multi form.
-// does a multi call run as `count` single launches (count 1, a plan without a multi form, a forced configuration, the
-// generator-shaped kernels)?  One predicate for the workspace size and the launcher.
-static bool multi_falls_back(const mtd_conv_args* a, int count, const Plan& pl) {
-    const bool gen_shape = a[0].C == 32 && a[0].g.TH * a[0].g.TW == 9 && geom_pixels(a[0].g) >= 32768;
-    return count == 1 || pl.cfg > 5 || g_force_cfg >= 6 || gen_shape;
-}
-
+// its own workspace of mtd_conv_igemm_multi_ws_bytes(a, count) bytes.  Runs as `count` single launches where the route says so
+// (conv_igemm_route: count 1, a plan without a multi form, a forced configuration, the generator-shaped kernels); the workspace
+// is then the single launches' own.
 extern "C" size_t mtd_conv_igemm_multi_ws_bytes(const mtd_conv_args* a, int count) {
     if (!a || count < 1 || count > MULTI_MAX || check_args(a[0]) != MTD_OK) return 0;
-    Plan pl = make_plan(a[0], count);
-    if (multi_falls_back(a, count, pl)) return mtd_conv_igemm_ws_bytes(&a[0]);      // the single launches' own plan
-    if (pl.splitk <= 1) return 0;
-    return (size_t)pl.splitk * (size_t)geom_pixels(a[0].g) * a[0].N * sizeof(float);
+    return splitk_ws_bytes(a[0], conv_igemm_route(a[0], count, g_igemm_force).plan.splitk);
 }
 
 extern "C" int mtd_conv_igemm_multi(const mtd_conv_args* a, int count, void* stream) {
@@ -1788,8 +1642,8 @@ extern "C" int mtd_conv_igemm_multi(const mtd_conv_args* a, int count, void* str
             (a[i].add2 == nullptr) != (a[0].add2 == nullptr) || (a[i].mask == nullptr) != (a[0].mask == nullptr) ||
             (a[i].scale == nullptr) != (a[0].scale == nullptr) || (a[i].scale2 == nullptr) != (a[0].scale2 == nullptr)) return MTD_EINVAL;
     }
-    Plan pl = make_plan(a[0], count);
-    if (multi_falls_back(a, count, pl)) {
+    const ConvRoute r = conv_igemm_route(a[0], count, g_igemm_force);
+    if (!r.multi) {
         for (int i = 0; i < count; ++i) {
             int rc = mtd_conv_igemm(&a[i], stream);
             if (rc != MTD_OK) return rc;
@@ -1798,47 +1652,19 @@ extern "C" int mtd_conv_igemm_multi(const mtd_conv_args* a, int count, void* str
     }
     IgemmMulti mp;
     for (int i = 0; i < MULTI_MAX; ++i) {
-        int rc = fill_params(&a[i < count ? i : 0], pl, mp.p[i]);
+        int rc = fill_params(&a[i < count ? i : 0], r.plan, mp.p[i]);
         if (rc != MTD_OK) return rc;
+        mp.p[i].fin = 0;      // (the multi form has no in-kernel finish: igemm_dispatch)
     }
-    // (split-K sets finish through splitk_epilogue_multi_kernel: with the in-kernel finish inlined four times the compiler
-    // merges the tails and selects the argument set dynamically -- 2.4 KB of scratch per lane)
-    for (int i = 0; i < MULTI_MAX; ++i) mp.p[i].fin = 0;
     hipStream_t s = (hipStream_t)stream;
     const int M = mp.p[0].M;
     double bytes = 0.0;
     for (int i = 0; i < count; ++i) bytes += algorithmic_bytes(&a[i]);
-    dim3 grid((M + pl.BM - 1) / pl.BM, a[0].N / pl.BN, pl.splitk * count);
-    const int prof = mtd_prof_begin(0, 16 + pl.cfg, pl.splitk, (long long)M * count, a[0].N, a[0].C, a[0].g.TH * a[0].g.TW, s, bytes);   // (16 + cfg: igemm_multi_kernel<cfg>)
-    switch (pl.cfg) {
-        case 0: MTD_LAUNCH((igemm_multi_kernel<2, 1, 4, 1>), grid, dim3(256), 0, s, mp); break;
-        case 1: MTD_LAUNCH((igemm_multi_kernel<1, 1, 4, 1>), grid, dim3(256), 0, s, mp); break;
-        case 2: MTD_LAUNCH((igemm_multi_kernel<2, 2, 4, 1>), grid, dim3(256), 0, s, mp); break;
-        case 3: MTD_LAUNCH((igemm_multi_kernel<1, 1, 2, 2>), grid, dim3(256), 0, s, mp); break;
-        case 4: MTD_LAUNCH((igemm_multi_kernel<2, 2, 2, 2>), grid, dim3(256), 0, s, mp); break;
-        default: MTD_LAUNCH((igemm_multi_kernel<1, 1, 1, 4>), grid, dim3(256), 0, s, mp); break;
-    }
+    const int prof = mtd_prof_begin(0, r.kernel, r.plan.splitk, (long long)M * count, a[0].N, a[0].C, conv_taps(a[0]), s, bytes);
+    igemm_dispatch(r.kernel, r.plan, mp.p[0], &mp, count, nullptr, s);
     mtd_prof_end(prof, s);
     MTD_LAUNCH_CHECK();
-    if (pl.splitk > 1 && !mp.p[0].fin) {
-        bool vec = true;
-        for (int i = 0; i < count; ++i) vec = vec && splitk_vec_ok(a[i], M);
-        if (vec) {
-            const long long total = (long long)M * a[0].N;
-            int blocks = (int)((total / 4 + 255) / 256);
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(splitk_epilogue_multi_kernel, dim3(blocks, count), dim3(256), 0, s, mp);
-            MTD_LAUNCH_CHECK();
-        } else {
-            const long long total = (long long)M * a[0].N;
-            int blocks = (int)((total + 255) / 256);
-            if (blocks > 2048) blocks = 2048;
-            for (int i = 0; i < count; ++i) {
-                hipLaunchKernelGGL(splitk_epilogue_scalar_kernel, dim3(blocks), dim3(256), 0, s, mp.p[i]);
-                MTD_LAUNCH_CHECK();
-            }
-        }
-    }
+    if (r.plan.splitk > 1) return launch_splitk_finish(mp.p, count, true, s);
     return MTD_OK;
 }
 #endif  // MTD_NO_API

@@ -396,109 +396,6 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void wino32_conv_kernel(const W3
     }
 }
 
-// ---- host side
-struct W32Form { int groups, ps, base_y, base_x; int kmap[16]; };
-
-// Which form is this geometry?  forward: 4x4 taps at stride 2 (tap = 2 j + phase); class: 2x2 taps at stride 1
-bool wino32_form(const mtd_geom& g, W32Form& f) {
-    if (g.TH != g.TW || g.in_sy != g.in_sx || g.tap_dy != g.tap_dx) return false;
-    if (g.TH == 4 && g.in_sy == 2 && g.tap_dy == 1) {
-        f.groups = 4; f.ps = 2; f.base_y = g.off_y; f.base_x = g.off_x;
-        for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px)
-                for (int jy = 0; jy < 2; ++jy)
-                    for (int jx = 0; jx < 2; ++jx)
-                        f.kmap[(py * 2 + px) * 4 + jy * 2 + jx] = (g.ky0 + (2 * jy + py) * g.ky_step) * g.KW + (g.kx0 + (2 * jx + px) * g.kx_step);
-        return true;
-    }
-    if (g.TH == 2 && g.in_sy == 1 && (g.tap_dy == 1 || g.tap_dy == -1)) {
-        const bool rev = g.tap_dy < 0;
-        f.groups = 1; f.ps = 1; f.base_y = g.off_y - (rev ? 1 : 0); f.base_x = g.off_x - (rev ? 1 : 0);
-        for (int i = 0; i < 16; ++i) f.kmap[i] = 0;
-        for (int jy = 0; jy < 2; ++jy)
-            for (int jx = 0; jx < 2; ++jx) {
-                const int ty = rev ? 1 - jy : jy, tx = rev ? 1 - jx : jx;
-                f.kmap[jy * 2 + jx] = (g.ky0 + ty * g.ky_step) * g.KW + (g.kx0 + tx * g.kx_step);
-            }
-        return true;
-    }
-    return false;
-}
-
-bool wino32_eligible(const mtd_conv_args* a, int count) {
-    if (!a || count < 1 || count > 4) return false;
-    W32Form f0;
-    if (!wino32_form(a[0].g, f0)) return false;
-    for (int i = 0; i < count; ++i) {
-        const mtd_conv_args& s = a[i];
-        if (!s.in || !s.w || !s.out || s.C <= 0 || s.N <= 0 || s.in_ld < s.C || s.out_ld < s.N) return false;
-        if ((s.C % 16) || (s.N % 64) || s.out2 || s.act == MTD_ACT_RELU_ADD || (s.in_ld % 4) || !aligned16(s.in) || !aligned16(s.w)) return false;
-        W32Form f;
-        if (!wino32_form(s.g, f) || f.groups != f0.groups) return false;
-        const mtd_geom &g = s.g, &h = a[0].g;
-        if (g.out_sy < 1 || g.out_sx < 1) return false;
-        if ((g.OH - 1) * g.out_sy + g.out_oy >= g.OHF || (g.OW - 1) * g.out_sx + g.out_ox >= g.OWF) return false;
-        if (i) {      // one shape, one set of operands: the classes differ in offsets, filter entries and where their pixels land
-            if (g.B != h.B || g.IH != h.IH || g.IW != h.IW || g.OH != h.OH || g.OW != h.OW || g.OHF != h.OHF || g.OWF != h.OWF ||
-                g.out_sy != h.out_sy || g.out_sx != h.out_sx) return false;
-            if (s.in != a[0].in || s.in_ld != a[0].in_ld || s.C != a[0].C || s.N != a[0].N || s.out != a[0].out || s.out_ld != a[0].out_ld ||
-                s.scale != a[0].scale || s.scale2 != a[0].scale2 || s.scale_split != a[0].scale_split || s.bias != a[0].bias ||
-                s.add1 != a[0].add1 || s.add1_ld != a[0].add1_ld || s.add2 != a[0].add2 || s.add2_ld != a[0].add2_ld || s.act != a[0].act ||
-                s.mask != a[0].mask || s.mask_ld != a[0].mask_ld || s.mask_slope != a[0].mask_slope) return false;
-        }
-        const long long npix = (long long)g.B * g.IH * g.IW;
-        if (((npix - 1) * s.in_ld + s.C) * 4 >= (1ll << 31)) return false;
-        if (geom_pixels(g) * s.N >= (1ll << 31)) return false;
-        if ((long long)64 * f.groups * s.N * s.C >= (1ll << 31)) return false;
-        if ((long long)g.B * g.OHF * g.OWF * s.out_ld >= (1ll << 31)) return false;
-    }
-    return true;
-}
-
-struct W32Plan { int splitk, c_per_split, tiles_x, tiles_y, ntiles, lean, pays, nb; };
-
-W32Plan wino32_plan_nb(const mtd_conv_args& a, int count, int groups, int nb) {
-    W32Plan pl{};
-    pl.tiles_x = (a.g.OW + 2) / 3;
-    pl.tiles_y = (a.g.OH + 2) / 3;
-    pl.ntiles = a.g.B * pl.tiles_x * pl.tiles_y;
-    pl.nb = nb;
-    const long long blocks = (long long)((pl.ntiles + WT - 1) / WT) * (a.N / (32 * pl.nb)) * count;
-    const int chunks = groups * a.C / 16;
-    int sk = blocks <= 128 ? (int)(256 / blocks) : 1;
-    if (sk > chunks / 4) sk = chunks / 4;
-    if (sk > 16) sk = 16;
-    if (sk < 1) sk = 1;
-    static const int env_sk = [] { const char* e = mtd_lab_env("MTD_WINO_S2_SPLITK"); return e ? atoi(e) : 0; }();
-    if (env_sk > 0) sk = env_sk < chunks ? env_sk : chunks;
-    const int cps = (chunks + sk - 1) / sk;
-    pl.splitk = (chunks + cps - 1) / cps;
-    pl.c_per_split = cps * 16;
-    static const int env_lean = [] { const char* e = mtd_lab_env("MTD_WINO_S2_LEAN"); return e ? atoi(e) : 1; }();
-    const long long grid = blocks * pl.splitk;
-    pl.lean = pl.nb == 2 && env_lean && (env_lean == 2 || (cps <= 8 && grid >= 384));
-    // Does the form pay against the implicit GEMM (tools/wino_s2_probe.py, profiles/r5_wino_s2_probe.txt)?  A workgroup is 32 tiles x 64
-    // (or 128) channels with a fixed cost outside its K loop, so: forward -- where the grid fills the 256 CUs' rounds to 80 % (1.2 .. 1.5x
-    // on down1 / down3 at both batch sizes and down2 at 32 images); data gradient -- K is the layer's output channels, only down1's four
-    // steps in the two-per-CU form come out ahead (1.36 .. 1.42x; down2: 1.09x at 64 images, 0.72x at 32).
-    const double fill = (double)grid / (double)(((grid + 255) / 256) * 256);
-    pl.pays = groups == 4 ? (fill >= 0.8) : (pl.lean && chunks <= 4);
-    return pl;
-}
-
-W32Plan wino32_plan(const mtd_conv_args& a, int count, int groups) {
-    static const int env_nb = [] { const char* e = mtd_lab_env("MTD_WINO_S2_NB"); return e ? atoi(e) : 0; }();
-    if (env_nb == 4 && a.N % 128 == 0) return wino32_plan_nb(a, count, groups, 4);
-    W32Plan pl = wino32_plan_nb(a, count, groups, 2);
-    // forward grids the 64-channel workgroups leave short (down2 at 64 images: 144 of them, 0.93x): 128-channel workgroups and the
-    // split of K that goes with them (72 x 3: 1.19x)
-    if (!pl.pays && groups == 4 && a.N % 128 == 0 && env_nb != 2) {
-        const W32Plan p4 = wino32_plan_nb(a, count, groups, 4);
-        if (p4.pays) pl = p4;
-    }
-    return pl;
-}
-
 }  // namespace
 
 extern "C" int mtd_winograd_s2_kmap(const mtd_geom* g, int* groups, int* kmap16) {
@@ -529,6 +426,62 @@ extern "C" int mtd_winograd_s2_weights(const mtd_wino_s2_weight_desc* table_dev,
     return MTD_OK;
 }
 
+// ---- the conv: the parameter fill, the dispatch and the C API.  The planner -- wino32_form, wino32_eligible, wino32_plan -- is
+// conv_plan.h.
+namespace {
+
+// the launch parameters of the sets a[0 .. count) of form f0 under plan pl
+int wino32_fill(const mtd_conv_args* a, int count, const W32Form& f0, const W32Plan& pl, W32Params& wp) {
+    IgemmParams& p = wp.p;
+    p.a = a[0];
+    p.M = (int)geom_pixels(a[0].g);
+    p.splitk = pl.splitk;
+    p.c_per_split = pl.c_per_split;
+    {
+        const long long npix = (long long)a[0].g.B * a[0].g.IH * a[0].g.IW;
+        p.in_bytes = (unsigned)(((npix - 1) * a[0].in_ld + a[0].C) * 4);
+    }
+    p.w_bytes = 0;
+    for (int t = 0; t < 16; ++t) p.tap_dy[t] = p.tap_dx[t] = p.tap_delta[t] = p.tap_kidx[t] = 0;
+    p.out_identity = out_identity(a[0].g);
+    p.out_linear = 0;
+    p.xcd_map = 0;
+    p.nt_store = 0;
+    p.fin = 0;
+    p.wide = conv_wide(a, count, pl.splitk);
+    wp.tiles_x = pl.tiles_x;
+    wp.tiles_y = pl.tiles_y;
+    wp.ntiles = pl.ntiles;
+    wp.groups = f0.groups;
+    wp.gsteps = a[0].C / 16;
+    wp.ps = f0.ps;
+    wp.nchunk = f0.groups * a[0].C / 8;
+    wp.nsets = count;
+    wp.w_bytes = (unsigned)((long long)64 * f0.groups * a[0].N * a[0].C);
+    wp.xcd_order = wino32_xcd_order(a[0], count, f0.groups);
+    const size_t need = splitk_ws_bytes(a[0], pl.splitk);
+    for (int i = 0; i < 4; ++i) {
+        const mtd_conv_args& s = a[i < count ? i : 0];
+        W32Form f;
+        wino32_form(s.g, f);
+        if (need && (!s.ws || s.ws_bytes < need)) return MTD_EWS;
+        wp.set[i] = W32Set{s.w, s.ws, f.base_y, f.base_x, s.g.out_oy, s.g.out_ox};
+    }
+    return MTD_OK;
+}
+
+// the dispatch: ONE launch of kernel k
+void wino32_dispatch(int k, dim3 grid, const W32Params& wp, hipStream_t s) {
+    switch (k) {
+        case CK_WINO32_NB4: MTD_LAUNCH((wino32_conv_kernel<4>), grid, dim3(512), 0, s, wp); break;
+        case CK_WINO32_NB2_LEAN: MTD_LAUNCH((wino32_conv_kernel<2, true>), grid, dim3(512), 0, s, wp); break;
+        case CK_WINO32_NB2: MTD_LAUNCH((wino32_conv_kernel<2>), grid, dim3(512), 0, s, wp); break;
+        default: break;     // (no other kernel of the family is launched from this file)
+    }
+}
+
+}  // namespace
+
 // 0: not in the kernel's domain; 1: in the domain; 2: and the plan expects it to beat the implicit GEMM on this shape
 extern "C" int mtd_conv_winograd_s2_ok(const mtd_conv_args* a, int count) {
     if (!wino32_eligible(a, count)) return 0;
@@ -542,8 +495,7 @@ extern "C" size_t mtd_conv_winograd_s2_ws_bytes(const mtd_conv_args* a, int coun
     if (!wino32_eligible(a, count)) return 0;
     W32Form f;
     wino32_form(a[0].g, f);
-    const W32Plan pl = wino32_plan(a[0], count, f.groups);
-    return pl.splitk > 1 ? (size_t)pl.splitk * (size_t)geom_pixels(a[0].g) * a[0].N * sizeof(float) : 0;
+    return splitk_ws_bytes(a[0], wino32_plan(a[0], count, f.groups).splitk);
 }
 
 // a[0 .. count): as for mtd_conv_igemm_multi, except that a[i].w points to the TRANSFORMED weights of set i
@@ -554,73 +506,27 @@ extern "C" int mtd_conv_winograd_s2(const mtd_conv_args* a, int count, void* str
     wino32_form(a[0].g, f0);
     const W32Plan pl = wino32_plan(a[0], count, f0.groups);
     W32Params wp;
-    IgemmParams& p = wp.p;
-    p.a = a[0];
-    p.M = (int)geom_pixels(a[0].g);
-    p.splitk = pl.splitk;
-    p.c_per_split = pl.c_per_split;
     {
-        const long long npix = (long long)a[0].g.B * a[0].g.IH * a[0].g.IW;
-        p.in_bytes = (unsigned)(((npix - 1) * a[0].in_ld + a[0].C) * 4);
+        const int rc = wino32_fill(a, count, f0, pl, wp);
+        if (rc != MTD_OK) return rc;
     }
-    p.w_bytes = 0;
-    for (int t = 0; t < 16; ++t) p.tap_dy[t] = p.tap_dx[t] = p.tap_delta[t] = p.tap_kidx[t] = 0;
-    {
-        const mtd_geom& g = a[0].g;
-        p.out_identity = (g.out_sy == 1 && g.out_sx == 1 && g.out_oy == 0 && g.out_ox == 0 && g.OHF == g.OH && g.OWF == g.OW);
-    }
-    p.out_linear = 0;
-    p.xcd_map = 0;
-    p.nt_store = 0;
-    p.fin = 0;
-    bool slabs16 = pl.splitk > 1 && (a[0].N % 4) == 0;
-    for (int i = 0; i < count; ++i) slabs16 = slabs16 && aligned16(a[i].ws);
-    p.wide = (wide_epilogue_ok(a[0]) ? 1 : 0) | (slabs16 ? 2 : 0);
-    wp.tiles_x = pl.tiles_x;
-    wp.tiles_y = pl.tiles_y;
-    wp.ntiles = pl.ntiles;
-    wp.groups = f0.groups;
-    wp.gsteps = a[0].C / 16;
-    wp.ps = f0.ps;
-    wp.nchunk = f0.groups * a[0].C / 8;
-    wp.nsets = count;
-    wp.w_bytes = (unsigned)((long long)64 * f0.groups * a[0].N * a[0].C);
-    {
-        const double wbytes = 64.0 * f0.groups * a[0].C * a[0].N * count, ibytes = (double)a[0].g.B * a[0].g.IH * a[0].g.IW * a[0].C * 4;
-        wp.xcd_order = wbytes >= ibytes ? 1 : 2;
-    }
-    const size_t need = pl.splitk > 1 ? (size_t)pl.splitk * (size_t)p.M * a[0].N * sizeof(float) : 0;
-    for (int i = 0; i < 4; ++i) {
-        const mtd_conv_args& s = a[i < count ? i : 0];
-        W32Form f;
-        wino32_form(s.g, f);
-        if (need && (!s.ws || s.ws_bytes < need)) return MTD_EWS;
-        wp.set[i] = W32Set{s.w, s.ws, f.base_y, f.base_x, s.g.out_oy, s.g.out_ox};
-    }
+    const IgemmParams& p = wp.p;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((wp.ntiles + WT - 1) / WT, a[0].N / (32 * pl.nb), pl.splitk * count);
     double bytes = 0.0;
     for (int i = 0; i < count; ++i) bytes += algorithmic_bytes(&a[i]);
-    const int prof = mtd_prof_begin(0, pl.nb == 4 ? 31 : pl.lean ? 30 : 29, pl.splitk, (long long)p.M * count, a[0].N, a[0].C, a[0].g.TH * a[0].g.TW, s, bytes);
-    if (pl.nb == 4) MTD_LAUNCH((wino32_conv_kernel<4>), grid, dim3(512), 0, s, wp);
-    else if (pl.lean) MTD_LAUNCH((wino32_conv_kernel<2, true>), grid, dim3(512), 0, s, wp);
-    else MTD_LAUNCH((wino32_conv_kernel<2>), grid, dim3(512), 0, s, wp);
+    const int prof = mtd_prof_begin(0, pl.kernel, pl.splitk, (long long)p.M * count, a[0].N, a[0].C, conv_taps(a[0]), s, bytes);
+    wino32_dispatch(pl.kernel, grid, wp, s);
     mtd_prof_end(prof, s);
     MTD_LAUNCH_CHECK();
-    if (pl.splitk > 1) {
+    if (pl.splitk > 1) {      // every set's slabs with the set's own arguments and output mapping
+        IgemmParams slabs[4];
         for (int i = 0; i < count; ++i) {
-            IgemmParams q = p;
-            q.a = a[i];
-            const mtd_geom& g = a[i].g;
-            q.out_identity = (g.out_sy == 1 && g.out_sx == 1 && g.out_oy == 0 && g.out_ox == 0 && g.OHF == g.OH && g.OWF == g.OW);
-            const long long total = (long long)p.M * a[i].N;
-            const bool vec = splitk_vec_ok(a[i], p.M);
-            int blocks = (int)(((vec ? total / 4 : total) + 255) / 256);
-            if (blocks > 2048) blocks = 2048;
-            if (vec) hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, s, q);
-            else hipLaunchKernelGGL(splitk_epilogue_scalar_kernel, dim3(blocks), dim3(256), 0, s, q);
-            MTD_LAUNCH_CHECK();
+            slabs[i] = p;
+            slabs[i].a = a[i];
+            slabs[i].out_identity = out_identity(a[i].g);
         }
+        return launch_splitk_finish(slabs, count, false, s);
     }
     return MTD_OK;
 }

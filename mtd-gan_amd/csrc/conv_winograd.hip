@@ -59,7 +59,6 @@
 #endif
 namespace {
 
-constexpr int WT = 32;        // tiles per workgroup
 constexpr int WALD = 20;      // LDS row stride (floats) of As[xi][tile][16 c]: 16-byte aligned, b128 reads of 16 rows hit 16 x 4 distinct banks
 constexpr int WXLD = 36;      // LDS row stride (floats) of the exchange image X[xi][tile][32 n]: 16-byte aligned rows
 
@@ -594,7 +593,6 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void wino_conv_kernel(const Wino
 // differ).  On the 2x2 ... 8x8 maps a single layer fills a fraction of the chip even with its split of K; two of them in one launch are
 // twice the workgroups for one launch latency (and one slab-sum launch for both).  grid.z = 2 x the split of K: the first half of it
 // is problem 0.  (A branch per problem, not an index: a dynamic index into the kernel arguments would put them in scratch.)
-constexpr int WINO_MULTI_MAX = 3;
 struct WinoMulti { WinoParams p[WINO_MULTI_MAX]; int count; };
 
 template <int NB, bool LEAN = false, int PX = 4>
@@ -611,128 +609,6 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void wino_conv_multi_kernel(cons
 
 #include "conv_wino_c32.h"
 #include "conv_winograd_split.h"
-
-int wino_patch_w_of(const mtd_conv_args& a);
-
-// the kernel's domain: 3x3, stride 1, "same" size, even height and width, every tap within one pixel of the output position,
-// output pixel == launch pixel, C a multiple of 16, N a multiple of 64 (or C = N = 32 in the F(2x4) form), the input view inside 32-bit byte offsets
-bool wino_eligible(const mtd_conv_args& a) {
-    const mtd_geom& g = a.g;
-    if (g.TH != 3 || g.TW != 3 || g.in_sy != 1 || g.in_sx != 1) return false;
-    if (g.IH != g.OH || g.IW != g.OW || (g.OH & 1) || (g.OW & 1)) return false;
-    if (!(g.out_sy == 1 && g.out_sx == 1 && g.out_oy == 0 && g.out_ox == 0 && g.OHF == g.OH && g.OWF == g.OW)) return false;
-    for (int i = 0; i < 3; ++i) {
-        const int dy = g.off_y + i * g.tap_dy, dx = g.off_x + i * g.tap_dx;
-        if (dy < -1 || dy > 1 || dx < -1 || dx > 1) return false;
-    }
-    if (g.tap_dy == 0 || g.tap_dx == 0) return false;
-    if (a.C % 16) return false;
-    if (a.out2 && !(a.N == 32 && a.C == 32 && a.mask)) return false;      // (a second output: the persistent 32 -> 32 kernel's MASKED2 form only; mtd_conv_winograd_ok checks that it takes the launch)
-    // N a multiple of 64; or the generator's 32 -> 32 channel layers in the F(2x4) form: the persistent kernel of conv_wino_c32.h
-    // (wino_c32_takes), else this kernel's 32-channel workgroups (NB = 1).  (Whether conv() sends them here is the host's
-    // threshold, kernels.WINO_C32_MIN_HW: whole-slice inference yes, the 64 x 64 training patches no -- DESIGN 3.8.)
-    if ((a.N % 64) && !(a.N == 32 && a.C == 32 && wino_patch_w_of(a) == 6)) return false;
-    if (a.act == MTD_ACT_RELU_ADD && !((a.N % 64) != 0 && !a.mask)) return false;      // residual after the activation: that form only
-    return true;
-}
-
-struct WinoPlan { int nb, lean, splitk, c_per_split, px; };
-
-// Which transform along x does this layer take?  4 = the patch width of F(2x2, 3x3), 6 = F(2x4, 3x3): maps whose width is a
-// multiple of 4 and at least MTD_WINO_F4_MIN_W (default 8: on the 4-pixel-wide maps a tile row is one tile and the transformed
-// weights -- 24 / 9 of the filter instead of 16 / 9 -- are what the launch streams).  MTD_WINO_F4=0 switches the form off.
-int g_f4_min_w = -1;          // -1: not yet read from the environment; 0: the form is off
-int wino_patch_w(const mtd_conv_args& a);
-int wino_patch_w_of(const mtd_conv_args& a) { return wino_patch_w(a); }
-int wino_patch_w(const mtd_conv_args& a) {
-    if (g_f4_min_w < 0) {
-        const char* off = mtd_lab_env("MTD_WINO_F4");
-        const char* mw = mtd_lab_env("MTD_WINO_F4_MIN_W");
-        g_f4_min_w = (off && atoi(off) == 0) ? 0 : (mw ? atoi(mw) : 8);
-    }
-    const int pxw = (g_f4_min_w > 0 && (a.g.OW % 4) == 0 && a.g.OW >= g_f4_min_w) ? 6 : 4;
-    // the split-bf16 kernel (conv_winograd_split.h) takes every layer whose N is a multiple of 64 (bit 4 of the code); the
-    // generator's 32 -> 32 layers keep the fp32 forms (the persistent kernel of conv_wino_c32.h)
-    return pxw | ((mtd_option(MTD_OPT_WINO_SPLIT) && (a.N % 64) == 0) ? 16 : 0);
-}
-
-WinoPlan wino_plan(const mtd_conv_args& a, int pxcode, int sets = 1) {
-    WinoPlan pl{};
-    const int px = pxcode & 15;
-    const bool split3 = (pxcode & 16) != 0;
-    pl.px = px;
-    const int tile_px = 2 * (px - 2);                            // output pixels per tile
-    pl.nb = (a.N % 128 == 0 && px == 4) ? 4 : 2;
-    // F(2x4): a tile block is 256 pixels x 64 channels; where that leaves the grid short (the mid-size maps: 4096 .. 16384 pixels)
-    // 32-channel workgroups (NB = 1) can stand in for a split of K -- no slabs, no finishing launch, but every 32 output channels
-    // repeat the input transform, and a transform instruction is paid in full beside the fp32 MFMAs.  The form won
-    // 0.2 ms per step while the transform cost 170 vector instructions per K step; at 116 the split of K is ahead by 0.15 ms
-    // (29.15 against 29.31 ms), so it is off by default now (MTD_WINO_F4_NB1=1: on).
-    static const int env_f4_nb1 = [] { const char* e = mtd_lab_env("MTD_WINO_F4_NB1"); return e ? atoi(e) : 0; }();
-    if (px == 6 && env_f4_nb1) {
-        const long long t = geom_pixels(a.g) / tile_px;
-        if (((t + WT - 1) / WT) * (a.N / 64) <= 128 && a.C >= 128) pl.nb = 1;
-    }
-    if (a.N % 64) pl.nb = 1;                                     // (F(2x4) only: wino_eligible)
-    if (split3) pl.nb = 2;                                       // the split-bf16 kernel: 64-channel workgroups only
-    // (lab, MTD_WINO_NB2_MAXC=64: the narrow form with its lean variant for layers with four K steps whatever their N -- 5 % less time
-    // for those launches (123 -> 116 us, 226 -> 213 us), 0.08 ms per step, but the input is then read per 64 instead of per 128 output
-    // channels: 62 -> 80 MB of fabric traffic per launch.  Off.)
-    static const int env_nb2_c = [] { const char* e = mtd_lab_env("MTD_WINO_NB2_MAXC"); return e ? atoi(e) : 0; }();
-    if (a.C <= env_nb2_c) pl.nb = 2;
-    const long long tiles = geom_pixels(a.g) / tile_px;
-    long long blocks = ((tiles + WT - 1) / WT) * (a.N / (32 * pl.nb));
-    if (blocks < 192 && pl.nb == 4 && a.N % 64 == 0 && !split3) {          // more, narrower workgroups before splitting K
-        pl.nb = 2;
-        blocks = ((tiles + WT - 1) / WT) * (a.N / 64);
-    }
-    const int chunks = a.C / 16;                                 // K steps of 16 channels
-    // K steps per slice at least: 2 since the end of round 5 (rounds 3-5: 4).  In the concurrent step the layers this frees -- C = 64 ... 128 on
-    // grids of 64 ... 128 workgroups -- gain more from the second half of the chip than the extra slab costs: 27.45 -> 27.33 ms in four A/B
-    // pairs (1: 27.37 / 27.44, 3: 27.42 / 27.40; a cap on the split or a target of 384 / 512 workgroups loses 0.4 ... 1.8 ms)
-    static const int env_sk_steps = [] { const char* e = mtd_lab_env("MTD_WINO_SPLITK_MINSTEPS"); return e ? atoi(e) : 2; }();
-    // (sets > 1: the group form.s grid holds that many problems and the split of K is planned for the whole grid: wino_group_sets)
-    const long long grid_blocks = blocks * sets;
-    int sk = grid_blocks <= 128 ? (int)(256 / grid_blocks) : 1;
-    if (sk > chunks / env_sk_steps) sk = chunks / env_sk_steps;
-    if (sk > 16) sk = 16;
-    if (sk < 1) sk = 1;
-    static const int env_sk = [] { const char* e = mtd_lab_env("MTD_WINO_SPLITK"); return e ? atoi(e) : 0; }();
-    if (env_sk > 0) sk = env_sk < chunks ? env_sk : chunks;
-    const int cps = (chunks + sk - 1) / sk;
-    pl.splitk = (chunks + cps - 1) / cps;
-    pl.c_per_split = cps * 16;
-    // two lean workgroups per CU where a workgroup has few K steps and the grid has at least two per CU (MTD_WINO_LEAN: 0 never,
-    // 1 by this rule, 2 whenever NB = 2)
-    static const int env_lean = [] { const char* e = mtd_lab_env("MTD_WINO_LEAN"); return e ? atoi(e) : 1; }();
-    const long long grid = ((tiles + WT - 1) / WT) * (a.N / (32 * pl.nb)) * pl.splitk;
-    pl.lean = px == 4 && pl.nb == 2 && env_lean && (env_lean == 2 || (cps <= 8 && grid >= 512)) && !split3;
-    return pl;
-}
-
-// The persistent 32 -> 32 channel kernel (conv_wino_c32.h) takes a layer of the F(2x4) form with one residual operand at most,
-// no scales, no mask, 16-byte aligned rows everywhere and buffers inside 31-bit byte offsets.  MTD_WINO_C32_KERNEL=0: the
-// general kernel's 32-channel workgroups instead (lab switch).
-bool wino_c32_takes(const mtd_conv_args& a, int pxcode) {
-    const int px = pxcode;       // (a split code, 20 / 22, never matches 6: N % 64 == 0 there)
-    static const int env_on = [] { const char* e = mtd_lab_env("MTD_WINO_C32_KERNEL"); return e ? atoi(e) : 1; }();
-    if (!env_on || px != 6 || a.C != 32 || a.N != 32) return false;
-    if (a.scale || a.scale2 || a.add2 || (a.out2 && !a.mask)) return false;
-    if (a.mask && (a.act == MTD_ACT_RELU_ADD || !aligned16(a.mask) || (a.mask_ld % 4))) return false;
-    if (a.out2 && (!aligned16(a.out2) || (a.out2_ld % 4))) return false;
-    if (!wide_epilogue_ok(a) || !aligned16(a.in) || (a.in_ld % 4)) return false;
-    const long long M = geom_pixels(a.g);
-    if (M / 8 >= (1ll << 23)) return false;
-    if (((M - 1) * a.out_ld + a.N) * 4 >= (1ll << 31)) return false;
-    if (a.add1 && ((M - 1) * a.add1_ld + a.N) * 4 >= (1ll << 31)) return false;
-    if (a.mask && ((M - 1) * a.mask_ld + a.N) * 4 >= (1ll << 31)) return false;
-    if (a.out2 && ((M - 1) * a.out2_ld + a.N) * 4 >= (1ll << 31)) return false;
-    return true;
-}
-
-// the patch width the transformed weights in a->w were built for travels in a->w_st (6: F(2x4, 3x3); anything else: 4)
-// (bit 4: the split-bf16 form)
-inline int wino_args_px(const mtd_conv_args& a) { return ((a.w_st & 15) == 6 ? 6 : 4) | ((a.w_st & 16) && a.w_st < 32 ? 16 : 0); }
 
 }  // namespace
 
@@ -778,45 +654,12 @@ extern "C" int mtd_winograd_kmap(const mtd_geom* g, int* kmap9) {
     return MTD_OK;
 }
 
-extern "C" int mtd_conv_winograd_ok(const mtd_conv_args* a) {
-    if (!a || !a->in || !a->w || !a->out) return 0;
-    if (a->C <= 0 || a->N <= 0 || a->in_ld < a->C || a->out_ld < a->N) return 0;
-    if (!wino_eligible(*a)) return 0;
-    const long long npix = (long long)a->g.B * a->g.IH * a->g.IW;
-    if (((npix - 1) * a->in_ld + a->C) * 4 >= (1ll << 31)) return 0;
-    if (geom_pixels(a->g) * a->N >= (1ll << 31)) return 0;
-    if ((long long)144 * a->N * a->C >= (1ll << 31)) return 0;          // (the transformed weights inside 31-bit byte offsets, split form included)
-    // a mask on a 32 -> 32 layer / a second output: only the persistent kernel carries them in this form (the general kernel's
-    // 32-channel workgroups take a mask, never a second output -- and the caller's MASKED2 launches must not end up there)
-    if (a->out2 && !wino_c32_takes(*a, wino_patch_w(*a))) return 0;
-    return 1;
-}
+// ---- the convs: the parameter fills, the dispatch and the C API.  The planner -- wino_eligible, wino_patch_w, wino_plan,
+// wino_c32_takes, wino_group_ok -- is conv_plan.h.
+namespace {
 
-// The transform this layer's weights are to be built for (mtd_wino_weight_desc.px, and a->w_st of the conv launch): 6 =
-// F(2x4, 3x3), 4 = F(2x2, 3x3); 0 if the layer is not in the Winograd kernel's domain.
-extern "C" int mtd_conv_winograd_patch_w(const mtd_conv_args* a) {
-    if (!mtd_conv_winograd_ok(a)) return 0;
-    return wino_patch_w(*a);
-}
-
-// Tuning / test hook: narrowest map that takes F(2x4, 3x3) (0: never; the default is 8, or MTD_WINO_F4_MIN_W / MTD_WINO_F4=0 from
-// the environment).  Returns the previous value.  Callers that cache mtd_conv_winograd_patch_w's answers drop them.
-extern "C" int mtd_conv_winograd_f4_min_w(int min_w) {
-    mtd_conv_args probe{};
-    (void)wino_patch_w(probe);                       // (reads the environment once)
-    const int old = g_f4_min_w;
-    if (min_w >= 0) g_f4_min_w = min_w;
-    return old;
-}
-
-extern "C" size_t mtd_conv_winograd_ws_bytes(const mtd_conv_args* a) {
-    if (!mtd_conv_winograd_ok(a)) return 0;
-    const WinoPlan pl = wino_plan(*a, wino_args_px(*a));
-    return pl.splitk > 1 ? (size_t)pl.splitk * (size_t)geom_pixels(a->g) * a->N * sizeof(float) : 0;
-}
-
-// the launch parameters of one problem (shared by mtd_conv_winograd and mtd_conv_winograd_pair)
-static int wino_fill(const mtd_conv_args* a, const WinoPlan& pl, int pxcode, WinoParams& wp) {
+// the launch parameters of one problem (shared by mtd_conv_winograd and mtd_conv_winograd_group)
+int wino_fill(const mtd_conv_args* a, const WinoPlan& pl, int pxcode, WinoParams& wp) {
     const int px = pxcode & 15;
     const bool split3 = (pxcode & 16) != 0;
     IgemmParams& p = wp.p;
@@ -835,26 +678,19 @@ static int wino_fill(const mtd_conv_args* a, const WinoPlan& pl, int pxcode, Win
     p.xcd_map = 0;
     p.nt_store = 0;
     p.fin = 0;
-    p.wide = (wide_epilogue_ok(*a) ? 1 : 0) | ((pl.splitk > 1 && aligned16(a->ws) && (a->N % 4) == 0) ? 2 : 0);
+    p.wide = conv_wide(a, 1, pl.splitk);
     wp.tiles_x = a->g.OW / (px - 2);
     wp.tiles_per_image = (a->g.OH / 2) * wp.tiles_x;
     wp.ntiles = a->g.B * wp.tiles_per_image;
     wp.nchunk = a->C / 8;
     wp.w_bytes = (unsigned)((long long)4 * px * a->N * a->C * (split3 ? 6 : 4));
-    {
-        static const int env_xcd = [] { const char* e = mtd_lab_env("MTD_WINO_XCD"); return e ? atoi(e) : -1; }();
-        const double wbytes = 4.0 * px * a->C * a->N * 4, ibytes = (double)p.M * a->C * 4;
-        wp.xcd_order = env_xcd >= 0 ? env_xcd : (wbytes >= ibytes ? 1 : 2);
-    }
-    if (pl.splitk > 1) {
-        const size_t need = (size_t)pl.splitk * (size_t)p.M * a->N * sizeof(float);
-        if (!a->ws || a->ws_bytes < need) return MTD_EWS;
-    }
+    wp.xcd_order = wino_xcd_order(*a, px);
+    if (pl.splitk > 1 && (!a->ws || a->ws_bytes < splitk_ws_bytes(*a, pl.splitk))) return MTD_EWS;
     return MTD_OK;
 }
 
 // the persistent kernel's walk and buffer extents for operands of `esz` bytes per element (4: fp32; 2: binary16 storage) and its grid
-static C32Params c32_params(const mtd_conv_args& a, const WinoParams& wp, int esz, dim3& pgrid) {
+C32Params c32_params(const mtd_conv_args& a, const WinoParams& wp, int esz, dim3& pgrid) {
     C32Params cp;
     cp.wp = wp;
     const long long M = wp.p.M;
@@ -872,6 +708,66 @@ static C32Params c32_params(const mtd_conv_args& a, const WinoParams& wp, int es
     cp.d_ty = (step / wp.tiles_x) % cp.tiles_y;
     cp.d_img = step / wp.tiles_per_image;
     return cp;
+}
+
+// The dispatch: ONE launch of kernel k on `grid` with the parameters of its family -- cp: the persistent 32 -> 32 channel
+// kernel, wp: the general and the split-bf16 kernels, mp: the group form.  (The cases stand in the order in which the kernel
+// templates were always first used: that order is the order of the kernels in the code object.)
+void wino_dispatch(int k, dim3 grid, const C32Params* cp, const WinoParams* wp, const WinoMulti* mp, hipStream_t s) {
+    switch (k) {
+        case CK_WINO_C32_MASK_ADD: MTD_LAUNCH((wino_c32_kernel<true, true>), grid, dim3(512), 0, s, *cp); break;
+        case CK_WINO_C32_MASK: MTD_LAUNCH((wino_c32_kernel<false, true>), grid, dim3(512), 0, s, *cp); break;
+        case CK_WINO_C32_ADD: MTD_LAUNCH((wino_c32_kernel<true>), grid, dim3(512), 0, s, *cp); break;
+        case CK_WINO_C32: MTD_LAUNCH((wino_c32_kernel<false>), grid, dim3(512), 0, s, *cp); break;
+        case CK_WINO3_PX6: MTD_LAUNCH((wino_conv3_kernel<6>), grid, dim3(512), 0, s, *wp); break;
+        case CK_WINO3_PX4: MTD_LAUNCH((wino_conv3_kernel<4>), grid, dim3(512), 0, s, *wp); break;
+        case CK_WINO6_NB1: MTD_LAUNCH((wino_conv_kernel<1, false, 6>), grid, dim3(512), 0, s, *wp); break;
+        case CK_WINO6_NB2: MTD_LAUNCH((wino_conv_kernel<2, false, 6>), grid, dim3(512), 0, s, *wp); break;
+        case CK_WINO_NB4: MTD_LAUNCH((wino_conv_kernel<4>), grid, dim3(512), 0, s, *wp); break;
+        case CK_WINO_NB2_LEAN: MTD_LAUNCH((wino_conv_kernel<2, true>), grid, dim3(512), 0, s, *wp); break;
+        case CK_WINO_NB2: MTD_LAUNCH((wino_conv_kernel<2>), grid, dim3(512), 0, s, *wp); break;
+        case CK_WINO_C32_F16_ADD: MTD_LAUNCH((wino_c32_kernel<true, false, _Float16>), grid, dim3(512), 0, s, *cp); break;
+        case CK_WINO_C32_F16: MTD_LAUNCH((wino_c32_kernel<false, false, _Float16>), grid, dim3(512), 0, s, *cp); break;
+        case CK_WINO_MULTI6_NB2: MTD_LAUNCH((wino_conv_multi_kernel<2, false, 6>), grid, dim3(512), 0, s, *mp); break;
+        case CK_WINO_MULTI_NB4: MTD_LAUNCH((wino_conv_multi_kernel<4>), grid, dim3(512), 0, s, *mp); break;
+        case CK_WINO_MULTI_NB2_LEAN: MTD_LAUNCH((wino_conv_multi_kernel<2, true>), grid, dim3(512), 0, s, *mp); break;
+        case CK_WINO_MULTI_NB2: MTD_LAUNCH((wino_conv_multi_kernel<2>), grid, dim3(512), 0, s, *mp); break;
+        default: break;     // (no other kernel of the family is launched from this file)
+    }
+}
+
+// The tuning hooks of this file, as the planner takes them: mtd_conv_winograd_f4_min_w (-1: the default) and the run-time
+// option "wino_split"
+int g_f4_min_w = -1;
+ConvForce wino_force() {
+    ConvForce f;
+    f.f4_min_w = g_f4_min_w;
+    f.wino_split = mtd_option(MTD_OPT_WINO_SPLIT);
+    return f;
+}
+
+}  // namespace
+
+extern "C" int mtd_conv_winograd_ok(const mtd_conv_args* a) { return wino_args_ok(a, wino_force()) ? 1 : 0; }
+
+// The transform this layer's weights are to be built for (mtd_wino_weight_desc.px, and a->w_st of the conv launch): 6 =
+// F(2x4, 3x3), 4 = F(2x2, 3x3); 0 if the layer is not in the Winograd kernel's domain.
+extern "C" int mtd_conv_winograd_patch_w(const mtd_conv_args* a) {
+    const ConvForce f = wino_force();
+    return wino_args_ok(a, f) ? wino_patch_w(*a, f) : 0;
+}
+
+// Tuning / test hook: narrowest map that takes F(2x4, 3x3) (0: never; the default is 8, or MTD_WINO_F4_MIN_W / MTD_WINO_F4=0 from
+// the environment of a lab build).  Returns the previous value.  Callers that cache mtd_conv_winograd_patch_w's answers drop them.
+extern "C" int mtd_conv_winograd_f4_min_w(int min_w) {
+    const int old = conv_f4_min_w(wino_force());
+    if (min_w >= 0) g_f4_min_w = min_w;
+    return old;
+}
+
+extern "C" size_t mtd_conv_winograd_ws_bytes(const mtd_conv_args* a) {
+    if (!mtd_conv_winograd_ok(a)) return 0;
+    return splitk_ws_bytes(*a, wino_plan(*a, wino_args_px(*a)).splitk);
 }
 
 // a: as for mtd_conv_igemm, except that a->w points to the TRANSFORMED weights of this view and geometry
@@ -895,38 +791,19 @@ extern "C" int mtd_conv_winograd(const mtd_conv_args* a, void* stream) {
     if (wino_c32_takes(*a, pxcode)) {
         dim3 pgrid;
         const C32Params cp = c32_params(*a, wp, 4, pgrid);
-        const int prof = mtd_prof_begin(0, a->mask ? (a->add1 ? 33 : 32) : (a->add1 ? 26 : 25), 1, p.M, a->N, a->C, 9, s, algorithmic_bytes(a));
-        if (a->mask && a->add1) MTD_LAUNCH((wino_c32_kernel<true, true>), pgrid, dim3(512), 0, s, cp);
-        else if (a->mask) MTD_LAUNCH((wino_c32_kernel<false, true>), pgrid, dim3(512), 0, s, cp);
-        else if (a->add1) MTD_LAUNCH((wino_c32_kernel<true>), pgrid, dim3(512), 0, s, cp);
-        else MTD_LAUNCH((wino_c32_kernel<false>), pgrid, dim3(512), 0, s, cp);
+        const ConvKernel k = wino_c32_kernel_of(*a, false);
+        const int prof = mtd_prof_begin(0, k, 1, p.M, a->N, a->C, 9, s, algorithmic_bytes(a));
+        wino_dispatch(k, pgrid, &cp, nullptr, nullptr, s);
         mtd_prof_end(prof, s);
         MTD_LAUNCH_CHECK();
         return MTD_OK;
     }
     const dim3 grid((wp.ntiles + WT - 1) / WT, a->N / (32 * pl.nb), pl.splitk);
-    // (one profiler id per INSTANTIATION -- 14: <2, false, 4>, 15: <4, false, 4>, 22: <2, true, 4>, 23: <2, false, 6>, 24: <1, false, 6>; 25, 26: wino_c32_kernel<false / true, false>; 32, 33: wino_c32_kernel<false / true, true> -- so that a record's name is
-    // one kernel symbol of a rocprofv3 table)
-    // (27, 28: wino_conv3_kernel<6 / 4>, the split-bf16 forms)
-    const int prof = mtd_prof_begin(0, split3 ? (px == 6 ? 27 : 28) : px == 6 ? (pl.nb == 1 ? 24 : 23) : (pl.nb == 4 ? 15 : (pl.lean ? 22 : 14)), pl.splitk, p.M, a->N, a->C, 9, s, algorithmic_bytes(a));
-    if (split3 && px == 6) MTD_LAUNCH((wino_conv3_kernel<6>), grid, dim3(512), 0, s, wp);
-    else if (split3) MTD_LAUNCH((wino_conv3_kernel<4>), grid, dim3(512), 0, s, wp);
-    else if (px == 6 && pl.nb == 1) MTD_LAUNCH((wino_conv_kernel<1, false, 6>), grid, dim3(512), 0, s, wp);
-    else if (px == 6) MTD_LAUNCH((wino_conv_kernel<2, false, 6>), grid, dim3(512), 0, s, wp);
-    else if (pl.nb == 4) MTD_LAUNCH((wino_conv_kernel<4>), grid, dim3(512), 0, s, wp);
-    else if (pl.lean) MTD_LAUNCH((wino_conv_kernel<2, true>), grid, dim3(512), 0, s, wp);
-    else MTD_LAUNCH((wino_conv_kernel<2>), grid, dim3(512), 0, s, wp);
+    const int prof = mtd_prof_begin(0, pl.kernel, pl.splitk, p.M, a->N, a->C, 9, s, algorithmic_bytes(a));
+    wino_dispatch(pl.kernel, grid, nullptr, &wp, nullptr, s);
     mtd_prof_end(prof, s);
     MTD_LAUNCH_CHECK();
-    if (pl.splitk > 1) {
-        const long long total = (long long)p.M * a->N;
-        const bool vec = splitk_vec_ok(*a, p.M);
-        int blocks = (int)(((vec ? total / 4 : total) + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        if (vec) hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(splitk_epilogue_scalar_kernel, dim3(blocks), dim3(256), 0, s, p);
-        MTD_LAUNCH_CHECK();
-    }
+    if (pl.splitk > 1) return launch_splitk_finish(&p, 1, false, s);
     return MTD_OK;
 }
 
@@ -955,11 +832,10 @@ extern "C" int mtd_conv_winograd_st(const mtd_conv_st_args* sa, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     dim3 pgrid;
     const C32Params cp = c32_params(*a, wp, 2, pgrid);
-    // (profiler ids 38, 39: wino_c32_kernel<false / true, false, _Float16>)
-    const int prof = mtd_prof_begin(0, a->add1 ? 39 : 38, 1, wp.p.M, a->N, a->C, 9, s,
+    const ConvKernel k = wino_c32_kernel_of(*a, true);
+    const int prof = mtd_prof_begin(0, k, 1, wp.p.M, a->N, a->C, 9, s,
                                     0.5 * algorithmic_bytes(a) + 2.0 * 9 * a->N * a->C);      // (the maps at 2 bytes, the weights at 4)
-    if (a->add1) MTD_LAUNCH((wino_c32_kernel<true, false, _Float16>), pgrid, dim3(512), 0, s, cp);
-    else MTD_LAUNCH((wino_c32_kernel<false, false, _Float16>), pgrid, dim3(512), 0, s, cp);
+    wino_dispatch(k, pgrid, &cp, nullptr, nullptr, s);
     mtd_prof_end(prof, s);
     MTD_LAUNCH_CHECK();
     return MTD_OK;
@@ -971,66 +847,32 @@ extern "C" int mtd_conv_winograd_st(const mtd_conv_st_args* sa, void* stream) {
 // The group's split of K is planned for the WHOLE grid (count problems: 1 / count of the slices per problem of a single launch -- fewer
 // slabs, and another grouping of the K sum: a group equals single launches up to rounding, a few 1e-6).  Measured in the step for pairs
 // against a plan per problem: 26.15 -> 25.80 ms (three A/B pairs; planning for 3 or 4 problems' worth of grid: +0.2 ms).
-// Lab: MTD_WINO_PAIR_SPLIT = n plans every group as if it held n problems (1: per problem).
-static int wino_group_sets(int count) {
-    static const int v = [] { const char* e = mtd_lab_env("MTD_WINO_PAIR_SPLIT"); return (e && atoi(e) > 0) ? atoi(e) : 0; }();
-    return v > 0 ? v : count;
-}
-
-extern "C" int mtd_conv_winograd_group_ok(const mtd_conv_args* a, int count) {
-    if (!a || count < 2 || count > WINO_MULTI_MAX) return 0;
-    const int px = wino_args_px(a[0]);
-    const long long M = geom_pixels(a[0].g);
-    for (int i = 0; i < count; ++i) {
-        if (!mtd_conv_winograd_ok(&a[i])) return 0;
-        if (__builtin_memcmp(&a[0].g, &a[i].g, sizeof(mtd_geom)) != 0 || a[0].N != a[i].N || a[0].C != a[i].C) return 0;
-        if (wino_args_px(a[i]) != px || wino_c32_takes(a[i], px) || !aligned16(a[i].w)) return 0;
-    }
-    if ((px & 16) || (a[0].N % 64)) return 0;
-    if ((px & 15) == 6 && (a[0].g.OW % 4)) return 0;
-    const WinoPlan pl = wino_plan(a[0], px, wino_group_sets(count));
-    if ((px & 15) == 6 && pl.nb != 2) return 0;
-    // the problems' slab sums go through ONE launch of the 16-byte epilogue: all need it (else: single launches)
-    if (pl.splitk > 1)
-        for (int i = 0; i < count; ++i)
-            if (!splitk_vec_ok(a[i], M)) return 0;
-    return 1;
-}
+extern "C" int mtd_conv_winograd_group_ok(const mtd_conv_args* a, int count) { return wino_group_ok(a, count, wino_force()) ? 1 : 0; }
 
 extern "C" int mtd_conv_winograd_group(const mtd_conv_args* a, int count, void* stream) {
     if (!mtd_conv_winograd_group_ok(a, count)) return MTD_EINVAL;
     const int pxcode = wino_args_px(a[0]);
-    const int px = pxcode & 15;
     const WinoPlan pl = wino_plan(a[0], pxcode, wino_group_sets(count));
     WinoMulti mp;
     mp.count = count;
+    IgemmParams slabs[WINO_MULTI_MAX];
     double bytes = 0.0;
     for (int i = 0; i < WINO_MULTI_MAX; ++i) {
         const int rc = wino_fill(&a[i < count ? i : 0], pl, pxcode, mp.p[i]);
         if (rc != MTD_OK) return rc;
         mp.p[i].xcd_order = mp.p[0].xcd_order;
+        slabs[i] = mp.p[i].p;
         if (i < count) bytes += algorithmic_bytes(&a[i]);
     }
     const IgemmParams& p = mp.p[0].p;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((mp.p[0].ntiles + WT - 1) / WT, a[0].N / (32 * pl.nb), count * pl.splitk);
-    // (profiler ids 34-37: wino_conv_multi_kernel<2, false, 6>, <2, false, 4>, <4, false, 4>, <2, true, 4>)
-    const int prof = mtd_prof_begin(0, px == 6 ? 34 : (pl.nb == 4 ? 36 : (pl.lean ? 37 : 35)), pl.splitk, (long long)count * p.M, a[0].N, a[0].C, 9, s, bytes);
-    if (px == 6) MTD_LAUNCH((wino_conv_multi_kernel<2, false, 6>), grid, dim3(512), 0, s, mp);
-    else if (pl.nb == 4) MTD_LAUNCH((wino_conv_multi_kernel<4>), grid, dim3(512), 0, s, mp);
-    else if (pl.lean) MTD_LAUNCH((wino_conv_multi_kernel<2, true>), grid, dim3(512), 0, s, mp);
-    else MTD_LAUNCH((wino_conv_multi_kernel<2>), grid, dim3(512), 0, s, mp);
+    const ConvKernel k = kConvKernel[pl.kernel].multi;
+    const int prof = mtd_prof_begin(0, k, pl.splitk, (long long)count * p.M, a[0].N, a[0].C, 9, s, bytes);
+    wino_dispatch(k, grid, nullptr, nullptr, &mp, s);
     mtd_prof_end(prof, s);
     MTD_LAUNCH_CHECK();
-    if (pl.splitk > 1) {
-        IgemmMulti em;
-        for (int i = 0; i < MULTI_MAX; ++i) em.p[i] = mp.p[i < count ? i : 0].p;      // (rows of the grid: blockIdx.y < count)
-        const long long total = (long long)p.M * a[0].N;
-        int blocks = (int)((total / 4 + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_epilogue_multi_kernel, dim3(blocks, count), dim3(256), 0, s, em);
-        MTD_LAUNCH_CHECK();
-    }
+    if (pl.splitk > 1) return launch_splitk_finish(slabs, count, true, s);      // (every problem takes the 16-byte form: wino_group_ok)
     return MTD_OK;
 }
 

@@ -424,20 +424,37 @@ def _count(kind, flops):
 _igemm_ws_cache = {}
 CALL_LOG = None     # tools/tune_igemm.py: a list collects ("igemm" | "wgrad", bytes(argument struct)) per call
 
-IGEMM_CONFIGS = ["igemm_kernel<2, 1, 4, 1>", "igemm_kernel<1, 1, 4, 1>", "igemm_kernel<2, 2, 4, 1>",
-                 "igemm_kernel<1, 1, 2, 2>", "igemm_kernel<2, 2, 2, 2>", "igemm_kernel<1, 1, 1, 4>",
-                 "igemm_tb_kernel<1>", "igemm_tb_kernel<2>", "igemm_v2_kernel<0>", "igemm_c32p_kernel", "igemm_c32t_kernel", "c32_bwd_kernel",
-                 "igemm_c32t_kernel<4, true, true, true>", "c32_bwd_kernel<1, true>", "wino_conv_kernel<2, false, 4>", "wino_conv_kernel<4, false, 4>",      # 12: Res-FFT block tail; 13: c32_bwd + irfft; 14, 15, 22, 23: Winograd
-                 "igemm_multi_kernel<2, 1, 4, 1>", "igemm_multi_kernel<1, 1, 4, 1>", "igemm_multi_kernel<2, 2, 4, 1>",      # 16 + cfg
-                 "igemm_multi_kernel<1, 1, 2, 2>", "igemm_multi_kernel<2, 2, 2, 2>", "igemm_multi_kernel<1, 1, 1, 4>",
-                 "wino_conv_kernel<2, true, 4>", "wino_conv_kernel<2, false, 6>", "wino_conv_kernel<1, false, 6>",             # 22, 23, 24 (6: F(2x4, 3x3))
-                 "wino_c32_kernel<false, false>", "wino_c32_kernel<true, false>",                                               # 25, 26: the persistent 32 -> 32 channel form
-                 "wino_conv3_kernel<6>", "wino_conv3_kernel<4>",                                                                # 27, 28: the split-bf16 forms (conv_winograd_split.h)
-                 "wino32_conv_kernel<2, false>", "wino32_conv_kernel<2, true>", "wino32_conv_kernel<4, false>",
-                 "wino_c32_kernel<false, true>", "wino_c32_kernel<true, true>",      # 32, 33: ... with a mask operand and a second output (round 6)
-                 "wino_conv_multi_kernel<2, false, 6>", "wino_conv_multi_kernel<2, false, 4>", "wino_conv_multi_kernel<4, false, 4>",      # 34-37: two problems of
-                 "wino_conv_multi_kernel<2, true, 4>",
-                 "wino_c32_kernel<false, false, _Float16>", "wino_c32_kernel<true, false, _Float16>"]      # 38, 39: binary16 activation storage (whole-slice inference)                                                                                         # one shape per launch (round 6)                                                                                       # 29: F(3x3, 2x2) for the 4x4 / stride-2 layers (conv_wino_s2.h)
+# Kernel numbers of the conv family (profiler family 0): enum ConvKernel and the table kConvKernel of csrc/conv_plan.h are the
+# source; these constants and IGEMM_CONFIGS mirror them (tests/test_conv_plan_cpu.py compares).  mtd_conv_igemm_override takes
+# the numbers below IGEMM_CFG_TILES (a tile kernel), IGEMM_CFG_C32P and IGEMM_CFG_C32T.
+IGEMM_CFG_128x32 = 1                           # igemm_kernel<1, 1, 4, 1>: the default tile
+IGEMM_CFG_32x128 = 5                           # igemm_kernel<1, 1, 1, 4>
+IGEMM_CFG_TB_128x32, IGEMM_CFG_TB_256x32 = 6, 7      # the tap-block kernels: at most nine taps
+IGEMM_CFG_TILES = 9                            # tile kernels: 0 .. 8
+IGEMM_CFG_C32P = 9                             # the persistent kernel of the generator-shaped layers
+IGEMM_CFG_C32T = 10                            # their halo-tile kernel (64-pixel rows)
+IGEMM_TILE_BM = (256, 128, 256, 64, 128, 32, 128, 256, 128)      # pixels x output channels of tile kernel 0 .. 8's workgroup
+IGEMM_TILE_BN = (32, 32, 64, 64, 128, 128, 32, 32, 128)
+IGEMM_CONFIGS = [
+    "igemm_kernel<2, 1, 4, 1>", "igemm_kernel<1, 1, 4, 1>", "igemm_kernel<2, 2, 4, 1>",                  # 0-5: the register-blocked tiles
+    "igemm_kernel<1, 1, 2, 2>", "igemm_kernel<2, 2, 2, 2>", "igemm_kernel<1, 1, 1, 4>",
+    "igemm_tb_kernel<1>", "igemm_tb_kernel<2>",                                                            # 6, 7: the tap-block kernels
+    "igemm_v2_kernel<0>",                                                                                  # 8: both operands through LDS
+    "igemm_c32p_kernel", "igemm_c32t_kernel",                                                              # 9, 10: the generator-shaped layers
+    "c32_bwd_kernel",                                                                                      # 11: data + weight gradient in one launch
+    "igemm_c32t_kernel<4, true, true, true>", "c32_bwd_kernel<1, true>",                                   # 12: Res-FFT block tail; 13: c32_bwd + irfft
+    "wino_conv_kernel<2, false, 4>", "wino_conv_kernel<4, false, 4>",                                      # 14, 15: Winograd F(2x2, 3x3)
+    "igemm_multi_kernel<2, 1, 4, 1>", "igemm_multi_kernel<1, 1, 4, 1>", "igemm_multi_kernel<2, 2, 4, 1>",  # 16-21: 16 + tile: several sets per launch
+    "igemm_multi_kernel<1, 1, 2, 2>", "igemm_multi_kernel<2, 2, 2, 2>", "igemm_multi_kernel<1, 1, 1, 4>",
+    "wino_conv_kernel<2, true, 4>",                                                                        # 22: ... its lean form
+    "wino_conv_kernel<2, false, 6>", "wino_conv_kernel<1, false, 6>",                                      # 23, 24: F(2x4, 3x3)
+    "wino_c32_kernel<false, false>", "wino_c32_kernel<true, false>",                                       # 25, 26: the persistent 32 -> 32 channel form
+    "wino_conv3_kernel<6>", "wino_conv3_kernel<4>",                                                        # 27, 28: the split-bf16 forms (conv_winograd_split.h)
+    "wino32_conv_kernel<2, false>", "wino32_conv_kernel<2, true>", "wino32_conv_kernel<4, false>",         # 29-31: F(3x3, 2x2) for the 4x4 / stride-2 layers (conv_wino_s2.h)
+    "wino_c32_kernel<false, true>", "wino_c32_kernel<true, true>",                                         # 32, 33: ... with a mask operand and a second output (round 6)
+    "wino_conv_multi_kernel<2, false, 6>", "wino_conv_multi_kernel<2, false, 4>",                          # 34-37: two or three problems of one shape per launch (round 6)
+    "wino_conv_multi_kernel<4, false, 4>", "wino_conv_multi_kernel<2, true, 4>",
+    "wino_c32_kernel<false, false, _Float16>", "wino_c32_kernel<true, false, _Float16>"]                   # 38, 39: binary16 activation storage (whole-slice inference)
 # kWgradCfg[i].name of csrc/conv_wgrad_plan.h ("?": a retired number)
 WGRAD_CONFIGS = ["wgrad_kernel<1, 1, 9>", "wgrad_kernel<1, 1, 4>", "wgrad_kernel<2, 2, 1>", "wgrad_kernel<1, 1, 8>",
                  "wgrad_kernel<1, 1, 3>", "wgrad_kernel<1, 1, 1>", "wgrad_kernel<2, 2, 3>",
@@ -484,7 +501,7 @@ def igemm_override(cfg, splitk=1):
     _igemm_ws_cache.clear()
 
 
-if _options.lab("MTD_IGEMM_CFG", ""):        # diagnostic switch, e.g. MTD_IGEMM_CFG=9: persistent kernel for the 32-channel 3x3 layers
+if _options.lab("MTD_IGEMM_CFG", ""):        # diagnostic switch, e.g. MTD_IGEMM_CFG=9 (IGEMM_CFG_C32P): persistent kernel for the 32-channel 3x3 layers
     igemm_override(int(_options.lab("MTD_IGEMM_CFG", "0")), 1)
 
 _raw_stream = torch._C._cuda_getCurrentRawStream       # (device index) -> hipStream_t as int; no Python Stream objects

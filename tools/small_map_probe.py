@@ -28,7 +28,7 @@ for B in (64, 32):
     bias = torch.randn(512, device="cuda")
     geom = K.geom_fwd(B, 1, 1, 1, 1, 0)
     row = f"M={B:4d}: plan {timed(lambda: K.conv(x, w, geom, 512, 512, 512, 1, out, bias=bias, act=K.ACT_LRELU, scale=scale)):6.1f} us"
-    for cfg in (1, 5):
+    for cfg in (K.IGEMM_CFG_128x32, K.IGEMM_CFG_32x128):
         for sk in (1, 2, 4, 8, 16):
             K.igemm_override(cfg, sk)
             try:

@@ -5,7 +5,7 @@
 
 Records the argument structs of one eager step, then times each distinct shape standalone (own buffers,
 no concurrency) with the library's automatic plan and -- with --sweep -- under every (tile config, split-K)
-override.  Prints one line per shape; used to derive make_plan() in conv_igemm.hip."""
+override.  Prints one line per shape; used to derive make_plan() in csrc/conv_plan.h."""
 import argparse
 import ctypes as C
 import os
@@ -18,8 +18,7 @@ import mtd_gan_amd  # noqa: F401
 from mtd_gan_amd import _lib, kernels as K
 from mtd_gan_amd.train_step import FullStepWorkload
 
-CFG_BM = [256, 128, 256, 64, 128, 32, 128, 256, 128]
-CFG_BN = [32, 32, 64, 64, 128, 128, 32, 32, 128]
+CFG_BM, CFG_BN = K.IGEMM_TILE_BM, K.IGEMM_TILE_BN
 
 
 def time_call(L, a, iters=20):
@@ -92,8 +91,8 @@ def main():
         table = []
         if args.sweep:
             chunks = a.C // 32
-            for cfg in range(9):
-                if a.N % CFG_BN[cfg] or (cfg in (6, 7) and T > 9):
+            for cfg in range(K.IGEMM_CFG_TILES):
+                if a.N % CFG_BN[cfg] or (cfg in (K.IGEMM_CFG_TB_128x32, K.IGEMM_CFG_TB_256x32) and T > 9):
                     continue
                 blocks = ((M + CFG_BM[cfg] - 1) // CFG_BM[cfg]) * (a.N // CFG_BN[cfg])
                 if blocks > 4096 and CFG_BM[cfg] < 128:
