@@ -535,6 +535,35 @@ size_t mtd_patch_gram_l1_ws_bytes(int B, int h, int w, int C);
 int mtd_patch_gram_l1(const float* X, const float* Y, int B, int h, int w, int C, double* out, void* ws, void* stream);
 int mtd_scaled_sums_f64(const double* in, int groups, int per, const double* scales_host, float* out, void* stream);
 
+/* ---- Frechet distance of the test loop (module/piq/fid.py; metrics.py:33-41, engine.py:179-181) -- DESIGN 3.8 -----------
+ * The statistic only: the feature network stays the caller's.  float64 throughout, products on v_mfma_f64_16x16x4_f64.  All
+ * matrices are contiguous row-major, D x D doubles, 1 <= D <= 16384, 8-byte aligned; no size is special (edge tiles and the
+ * tail of the sum are index-checked in the kernel) and NO buffer is padded: neither the caller's matrices nor the workspace,
+ * which holds D x D matrices exactly.  No floating-point atomics: every sum has a fixed order, two calls on the same inputs
+ * give the same bits.  Null pointers and sizes out of range: MTD_EINVAL, nothing launched.  The library allocates nothing.
+ *   mtd_fid_ws_bytes   bytes of `ws` for mtd_fid_distance / mtd_fid_residual at this D (six D x D matrices, the per-workgroup
+ *                      partials, the state); 0 = D out of range.  Used in stream order.
+ *   mtd_fid_stats      X (N, D) fp32 contiguous -> mu (D) = column means, sigma (D, D) = (X - mu)^T (X - mu) / (N - 1): two
+ *                      passes as fid.py:124-132,144-145, the centring in float64 on the way into the product.  N < 2: MTD_EINVAL
+ *                      (the reference divides by zero there).  ws is not used (may be NULL).
+ *   mtd_fid_gemm       C = alpha * A . B + beta_eye * I.  C must not overlap A or B.
+ *   mtd_fid_residual   out[0] = |A - scale * (Y . Y)|_F^2; the difference is not stored.
+ *   mtd_fid_distance   out[0] = |mu1 - mu2|^2 + tr s1 + tr s2 - 2 tr sqrt((s1 + offset I)(s2 + offset I)), out[1] = that trace
+ *                      of the square root, out[2] = the last err, out[3] = 1.0 if every element of the square root is finite,
+ *                      else 0.0 (fid.py:85); iters[0] = the round the iteration ended at.  Newton-Schulz as fid.py:42-61:
+ *                      Y0 = M / |M|_F, Z0 = I; per round T = 0.5 (3 I - Z Y), Y <- Y T, Z <- T Z, err = |M - S S|_F / |M|_F with
+ *                      S = sqrt(|M|_F) Y; ends at err <= 1e-5 or after max_iters rounds (the reference: 100).  The stop is taken
+ *                      ON THE DEVICE: max_iters rounds are enqueued, each launch reads a state word first and returns at once
+ *                      when it is set; the host reads nothing back during the call.  offset: 0, or the reference's 1e-6 of its
+ *                      second solve (fid.py:87-88; the traces of s1 and s2 stay those of the matrices as given).
+ *                      max_iters <= 0: MTD_EINVAL. */
+size_t mtd_fid_ws_bytes(int D);
+int mtd_fid_stats(const float* X, int N, int D, double* mu, double* sigma, void* ws, void* stream);
+int mtd_fid_gemm(const double* A, const double* B, double* C, int D, double alpha, double beta_eye, void* stream);
+int mtd_fid_residual(const double* A, const double* Y, double scale, int D, double* out, void* ws, void* stream);
+int mtd_fid_distance(const double* mu1, const double* s1, const double* mu2, const double* s2, int D, double offset,
+                     int max_iters, double* out, int* iters, void* ws, void* stream);
+
 /* ---- training-patch front end (create_datasets/Mayo.py:117-136, the "window_patch" pipeline, on the device) ----------
  * Input: the two dose levels of one or more CT slices in Hounsfield units as the reference's get_pixels_hu produces them
  * (int16, Mayo.py:19-43), resident in HBM.  mtd_foreground_bbox = CropForegroundd(source_key = full dose, select x > 0

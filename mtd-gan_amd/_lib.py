@@ -277,6 +277,12 @@ def lib():
     sig("mtd_patch_gram_l1_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_patch_gram_l1", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
     sig("mtd_scaled_sums_f64", ci, vp, ci, ci, C.POINTER(C.c_double), vp, vp)
+    cd = C.c_double
+    sig("mtd_fid_ws_bytes", sz, ci)
+    sig("mtd_fid_stats", ci, vp, ci, ci, vp, vp, vp, vp)
+    sig("mtd_fid_gemm", ci, vp, vp, vp, ci, cd, cd, vp)
+    sig("mtd_fid_residual", ci, vp, vp, cd, ci, vp, vp, vp)
+    sig("mtd_fid_distance", ci, vp, vp, vp, vp, ci, cd, ci, vp, vp, vp, vp)
     sig("mtd_edge_loss", ci, vp, vp, ci, cf, cf, vp, vp, cf, ci, vp, vp)
     sig("mtd_foreground_bbox", ci, vp, ci, ci, ci, cf, vp, vp)
     sig("mtd_window_patches", ci, vp, vp, ci, ci, ci, vp, vp, ci, cf, cf, ci, vp, vp, vp)
@@ -343,6 +349,7 @@ EXPORTS = [
     "mtd_conv_winograd_st", "mtd_conv_direct_st", "mtd_rfft_rows_any_h", "mtd_spec_mix_any_h", "mtd_irfft_rows_any_h",
     "mtd_sw_gather", "mtd_sw_blend", "mtd_sw_finish",
     "mtd_maxpool2x2", "mtd_patch_gram_l1_ws_bytes", "mtd_patch_gram_l1", "mtd_scaled_sums_f64",
+    "mtd_fid_ws_bytes", "mtd_fid_stats", "mtd_fid_gemm", "mtd_fid_residual", "mtd_fid_distance",
 ]
 
 

@@ -223,13 +223,19 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     the feature network: `model.perceptual_vgg = metrics.VGG19Features(state_dict)` -- the torchvision `vgg19` checkpoint is the
     caller's to hand over, none ships with this package.  The result then gains input_pl / gt_pl / pred_pl / input_tml / gt_tml /
     pred_tml and the CSV the reference's PL and TML columns (slices of at least 256 x 256: metrics.compute_TML); without the
-    attribute (or with None) the keys and the CSV are those of the pixel metrics alone.  FID (InceptionV3) is outside this
-    package.  Slice sizes as in valid_MTD_GAN_Ours (any 16..512 per side with `model.Generator.allow_any_size = True`; the 128 / 256 / 512 squares with
+    attribute (or with None) the keys and the CSV are those of the pixel metrics alone.  FID (engine.py:145-146,179-181) is
+    computed when the model carries a feature extractor: `model.fid_features = extractor`, any callable on a (B, 3, H, W) batch
+    (metrics.compute_feat; the reference's InceptionV3 is the caller's to build, none ships with this package).  The three feature
+    rows of every slice stay on the device and the result gains input_fid / gt_fid / pred_fid after the loop
+    (metrics.compute_FID: float64 statistics and matrix square root on the HIP kernels, DESIGN 3.8; at least two slices);
+    without the attribute (or with None) nothing changes.  Slice sizes as in valid_MTD_GAN_Ours (any 16..512 per side with `model.Generator.allow_any_size = True`; the 128 / 256 / 512 squares with
     binary16 activation storage under `model.Generator.activation_dtype = torch.float16`: predictions and metrics stay fp32;
     window by window under `model.Generator.sliding_window = dict(...)`)."""
     from . import metrics as M
     model.Generator.eval()
     vgg = getattr(model, "perceptual_vgg", None)
+    fid_features = getattr(model, "fid_features", None)
+    feats = ([], [], [])
     meters = {}
     rows = []
     for batch_data in data_loader:
@@ -246,6 +252,9 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
                 for who, v in zip(("input", "gt", "pred"), six[3 * j:3 * j + 3]):
                     meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
             perceptual = (six[2], six[5])
+        if fid_features is not None:
+            for rows_, f in zip(feats, M.compute_feat(x, y, clipped, extractor=fid_features)):
+                rows_.append(f.float())
         pm = M.pixel_metrics(x, y, clipped)
         for name, triple in pm.items():
             for who, v in zip(("input", "gt", "pred"), triple):
@@ -259,4 +268,8 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
             f.write(",PATH,PL,TML,RMSE,PSNR,SSIM\n" if vgg is not None else ",PATH,RMSE,PSNR,SSIM\n")
             for i, r in enumerate(rows):
                 f.write(f"{i}," + ",".join(str(v) for v in r) + "\n")
+    if fid_features is not None:
+        fid = torch.stack(M.compute_FID(*(torch.cat(f, dim=0) for f in feats))).tolist()       # the three values in one device -> host copy
+        for who, v in zip(("input", "gt", "pred"), fid):
+            meters.setdefault(f"{who}_fid", _Meter()).update(v, 1)
     return {k: round(mm.global_avg, 7) for k, mm in meters.items()}

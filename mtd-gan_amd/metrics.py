@@ -7,7 +7,13 @@ Perceptual metrics (metrics.py:43-168: compute_PL / compute_TML on the five VGG-
 arguments plus the keyword `vgg`): the feature stack is `VGG19Features`, built from a torchvision `vgg19` state dict that the
 caller hands over (no pretrained weights ship with this package), its convolutions are `kernels.conv` launches, the pools
 `mtd_maxpool2x2`, the L1 means `kernels.loss_terms` and the per-patch Gram-matrix distance `mtd_patch_gram_l1`.
-Inference only: no gradient flows through them.  FID (InceptionV3 features and a matrix square root) is out of scope."""
+Inference only: no gradient flows through them.
+
+FID (metrics.py:17-41, module/piq/fid.py): the statistic -- float64 mean and covariance of a feature set, the Newton-Schulz
+square root of the covariance product with its data-dependent stop, the distance and the reference's singular fallback -- runs
+on the HIP kernels of csrc/fid.hip (fid_statistics / fid_distance64 / compute_FID).  The feature network
+(the reference: piq's InceptionV3 on a downloaded checkpoint) does NOT ship: compute_feat takes it as `extractor`, any callable,
+and it runs in whatever the caller built it from."""
 import numpy as np
 import torch
 
@@ -273,3 +279,96 @@ def perceptual_metrics(input, target, pred, vgg):
     _perceptual_inputs("perceptual_metrics", input, target, pred, vgg, 16 * TML_PATCH)
     levels = _stacked_features(vgg, target, (input, pred))
     return torch.cat([_pl_values(levels, (1, 0, 2)), _tml_values(levels, (1, 0, 2))])
+
+
+# ================================================================================================ FID
+FID_MAX_ITERS = 100                         # _sqrtm_newton_schulz(num_iters=100), fid.py:24
+FID_EPS = 1e-6                              # _compute_fid(eps=1e-6), fid.py:64
+
+
+def _fid_feats(name, feats):
+    if not torch.is_tensor(feats) or feats.dim() != 2:
+        raise AssertionError(f"{name} expects (N, D) feature tensors")
+    if feats.shape[0] < 2:
+        raise ValueError(f"{name}: at least two feature rows expected, got {feats.shape[0]} (the covariance divides by N - 1; "
+                         "the reference returns NaN here)")
+    if feats.shape[1] < 1:
+        raise ValueError(f"{name}: features of dimension 0")
+    if not feats.is_cuda:
+        raise RuntimeError(f"{name}: HIP path needs CUDA tensors (no CPU fallback)")
+    if feats.dtype != torch.float32:
+        raise TypeError(f"{name}: fp32 features expected, got {feats.dtype}")
+    return feats.detach().contiguous()
+
+
+@torch.no_grad()
+def fid_statistics(feats):
+    """fid.py:135-146 on the float64 copy the reference makes (fid.py:186-187): (mu (D,), sigma (D, D)) in float64 from (N, D) fp32
+    CUDA features, mean first, then the product of the centred columns (mtd_fid_stats).  N < 2 raises ValueError."""
+    x = _fid_feats("fid_statistics", feats)
+    N, D = x.shape
+    mu = torch.empty(D, dtype=torch.float64, device=x.device)
+    sigma = torch.empty((D, D), dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().mtd_fid_stats(x.data_ptr(), N, D, mu.data_ptr(), sigma.data_ptr(), None, K.stream_ptr()), "mtd_fid_stats")
+    return mu, sigma
+
+
+def _fid_solve(mu1, s1, mu2, s2, offset):
+    """One solve: (out, iters) on the device -- out = [fid, tr sqrt(S1 S2), last err, finite flag] in float64."""
+    D = mu1.numel()
+    L = _lib.lib()
+    out = torch.empty(4, dtype=torch.float64, device=mu1.device)
+    iters = torch.empty(1, dtype=torch.int32, device=mu1.device)
+    ws = K.workspace(L.mtd_fid_ws_bytes(D), mu1.device)
+    _lib.check(L.mtd_fid_distance(mu1.data_ptr(), s1.data_ptr(), mu2.data_ptr(), s2.data_ptr(), D, offset, FID_MAX_ITERS, out.data_ptr(),
+                                  iters.data_ptr(), ws.data_ptr(), K.stream_ptr()), "mtd_fid_distance")
+    return out, iters
+
+
+@torch.no_grad()
+def fid_distance64(stats1, stats2):
+    """fid.py:64-91 on two (mu, sigma) pairs of fid_statistics: a 0-dim float64 device tensor.  The iteration and its stop run
+    on the device; the host reads the result once per solve, for the reference's fallback: if the square root is not finite,
+    solve once more with 1e-6 on both diagonals (fid.py:84-88)."""
+    (mu1, s1), (mu2, s2) = stats1, stats2
+    D = mu1.numel()
+    for mu, s in (stats1, stats2):
+        if not (mu.is_cuda and s.is_cuda):
+            raise RuntimeError("fid_distance64: HIP path needs CUDA tensors (no CPU fallback)")
+        if mu.dtype != torch.float64 or s.dtype != torch.float64 or tuple(mu.shape) != (D,) or tuple(s.shape) != (D, D):
+            raise AssertionError("fid_distance64 expects two (mu (D,), sigma (D, D)) float64 pairs of one D")
+    mu1, s1, mu2, s2 = (t.contiguous() for t in (mu1, s1, mu2, s2))
+    out, _ = _fid_solve(mu1, s1, mu2, s2, 0.0)
+    if out.tolist()[3] == 0.0:
+        print(f"FID calculation produces singular product; adding {FID_EPS} to diagonal of cov estimates")
+        out, _ = _fid_solve(mu1, s1, mu2, s2, FID_EPS)
+    return out[0]
+
+
+@torch.no_grad()
+def compute_FID(input_feats, target_feats, pred_feats):
+    """metrics.py:33-41: (FID(input, target), FID(target, target), FID(pred, target)) as 0-dim float32 device tensors.  The
+    target's statistics are computed once and serve all three."""
+    st = fid_statistics(target_feats)
+    return tuple(fid_distance64(st if f is target_feats else fid_statistics(f), st).float() for f in (input_feats, target_feats, pred_feats))
+
+
+@torch.no_grad()
+def compute_feat(input, target, pred, device=None, *, extractor):
+    """metrics.py:17-31 with the feature network handed over: `extractor` is any callable on a (B, 3, H, W) batch -- it runs in
+    whatever the caller built it from, this package ships none (the reference: piq's InceptionV3).  It is applied to
+    x.repeat(1, 3, 1, 1) of each image set and returns a tensor, or a list / tuple of exactly one; the result is flattened to
+    (B, D).  `device` is accepted for the reference's signature; the tensors' device is used."""
+    if not callable(extractor):
+        raise TypeError("compute_feat: pass the feature network as extractor=<callable> (no feature network ships with this package)")
+    if not (input.shape == target.shape and target.shape == pred.shape):
+        raise AssertionError("compute_feat expects three tensors of the same shape")
+    feats = []
+    for x in (input, target, pred):
+        f = extractor(x.repeat(1, 3, 1, 1))
+        if isinstance(f, (list, tuple)):
+            if len(f) != 1:
+                raise AssertionError(f"feature_encoder must return list with features from one layer. Got {len(f)}")
+            f = f[0]
+        feats.append(f.flatten(1))
+    return tuple(feats)
