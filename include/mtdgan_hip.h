@@ -564,6 +564,31 @@ int mtd_fid_residual(const double* A, const double* Y, double scale, int D, doub
 int mtd_fid_distance(const double* mu1, const double* s1, const double* mu2, const double* s2, int D, double offset,
                      int max_iters, double* out, int* iters, void* ws, void* stream);
 
+/* ---- FID's InceptionV3 feature network (module/piq/feature_extractors/fid_inception.py:134-168 and the block forwards
+ * :198-316, built by metrics.py:17-31 compute_feat) -- DESIGN 3.9 --------------------------------------------------------
+ * The 94 convolutions are mtd_conv_* launches; these are the other pieces.  Maps are NHWC fp32 on the caller's stream; source and
+ * destination each have their own pixel stride (in_ld, out_ld >= C), so a pool reads a block's input and writes into a channel
+ * slice of the block's output.  16-byte accesses along channels where C, both strides and both bases allow, value by value
+ * otherwise: no alignment is required.  Null pointers, B <= 0, a stride smaller than the channel count, an unknown mode:
+ * MTD_EINVAL, nothing launched.
+ *   mtd_resize_bilinear  fid_inception.py:150-158: F.interpolate(size = (OH, OW), mode = "bilinear", align_corners = False), no
+ *                        antialiasing, then 2 x - 1 when normalize != 0.  The source value of (b, c, y, x) is
+ *                        in[b in_sb + c in_sc + (y W + x) in_sp] (an NCHW batch: in_sc = H W, in_sp = 1), 1 <= C <=
+ *                        MTD_RESIZE_MAX_C, any H, W >= 1; out is (B, OH, OW, C) with pixel stride out_ld.  Source coordinates in
+ *                        double; OH == H and OW == W copies bit for bit (before the 2 x - 1).
+ *   mtd_pool3x3          :103 and torchvision's InceptionB / InceptionD: MTD_POOL_MAX_S2 = max_pool2d(3, stride 2), floor, H, W >= 3;
+ *                        :311 MTD_POOL_MAX_S1P1 = max_pool2d(3, stride 1, padding 1), the padding never wins;
+ *                        :215,243,276 MTD_POOL_AVG_S1P1 = avg_pool2d(3, stride 1, padding 1, count_include_pad = False): the sum of
+ *                        the taps inside the image divided by their number (4 / 6 / 9).  NaN propagates as in torch.
+ *   mtd_global_avgpool   :127 AdaptiveAvgPool2d((1, 1)): out[b out_ld + c] = mean over the H W pixels, summed in pixel order in
+ *                        double by one thread per (b, c): the same bits on every grid, no atomics. */
+#define MTD_RESIZE_MAX_C 4
+enum { MTD_POOL_MAX_S2 = 0, MTD_POOL_MAX_S1P1 = 1, MTD_POOL_AVG_S1P1 = 2 };
+int mtd_resize_bilinear(const float* in, long long in_sb, long long in_sc, long long in_sp, float* out, int out_ld, int B, int C,
+                        int H, int W, int OH, int OW, int normalize, void* stream);
+int mtd_pool3x3(const float* in, int in_ld, float* out, int out_ld, int B, int H, int W, int C, int mode, void* stream);
+int mtd_global_avgpool(const float* in, int in_ld, float* out, int out_ld, int B, int H, int W, int C, void* stream);
+
 /* ---- training-patch front end (create_datasets/Mayo.py:117-136, the "window_patch" pipeline, on the device) ----------
  * Input: the two dose levels of one or more CT slices in Hounsfield units as the reference's get_pixels_hu produces them
  * (int16, Mayo.py:19-43), resident in HBM.  mtd_foreground_bbox = CropForegroundd(source_key = full dose, select x > 0

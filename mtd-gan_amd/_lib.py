@@ -283,6 +283,9 @@ def lib():
     sig("mtd_fid_gemm", ci, vp, vp, vp, ci, cd, cd, vp)
     sig("mtd_fid_residual", ci, vp, vp, cd, ci, vp, vp, vp)
     sig("mtd_fid_distance", ci, vp, vp, vp, vp, ci, cd, ci, vp, vp, vp, vp)
+    sig("mtd_resize_bilinear", ci, vp, ll, ll, ll, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp)
+    sig("mtd_pool3x3", ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp)
+    sig("mtd_global_avgpool", ci, vp, ci, vp, ci, ci, ci, ci, ci, vp)
     sig("mtd_edge_loss", ci, vp, vp, ci, cf, cf, vp, vp, cf, ci, vp, vp)
     sig("mtd_foreground_bbox", ci, vp, ci, ci, ci, cf, vp, vp)
     sig("mtd_window_patches", ci, vp, vp, ci, ci, ci, vp, vp, ci, cf, cf, ci, vp, vp, vp)
@@ -350,6 +353,7 @@ EXPORTS = [
     "mtd_sw_gather", "mtd_sw_blend", "mtd_sw_finish",
     "mtd_maxpool2x2", "mtd_patch_gram_l1_ws_bytes", "mtd_patch_gram_l1", "mtd_scaled_sums_f64",
     "mtd_fid_ws_bytes", "mtd_fid_stats", "mtd_fid_gemm", "mtd_fid_residual", "mtd_fid_distance",
+    "mtd_resize_bilinear", "mtd_pool3x3", "mtd_global_avgpool",
 ]
 
 

@@ -224,8 +224,9 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     caller's to hand over, none ships with this package.  The result then gains input_pl / gt_pl / pred_pl / input_tml / gt_tml /
     pred_tml and the CSV the reference's PL and TML columns (slices of at least 256 x 256: metrics.compute_TML); without the
     attribute (or with None) the keys and the CSV are those of the pixel metrics alone.  FID (engine.py:145-146,179-181) is
-    computed when the model carries a feature extractor: `model.fid_features = extractor`, any callable on a (B, 3, H, W) batch
-    (metrics.compute_feat; the reference's InceptionV3 is the caller's to build, none ships with this package).  The three feature
+    computed when the model carries a feature extractor: `model.fid_features = metrics.InceptionV3Features(state_dict)` (the
+    reference's network on the HIP kernels; the checkpoint is the caller's to hand over, none ships with this package)
+    or any callable on a (B, 3, H, W) batch (metrics.compute_feat).  The three feature
     rows of every slice stay on the device and the result gains input_fid / gt_fid / pred_fid after the loop
     (metrics.compute_FID: float64 statistics and matrix square root on the HIP kernels, DESIGN 3.8; at least two slices);
     without the attribute (or with None) nothing changes.  Slice sizes as in valid_MTD_GAN_Ours (any 16..512 per side with `model.Generator.allow_any_size = True`; the 128 / 256 / 512 squares with

@@ -582,6 +582,17 @@ def geom_fwd(B, IH, IW, k, s, p):
     return Geom(B, IH, IW, OH, OW, s, s, -p, -p, 1, 1, k, k, k, 0, 0, 1, 1, OH, OW, 1, 1, 0, 0)
 
 
+def geom_fwd_rect(B, IH, IW, k, s=(1, 1), p=(0, 0), rows=None):
+    """geom_fwd with a rectangular kernel k = (kh, kw), stride s = (sh, sw) and zero padding p = (ph, pw): the 1x7 / 7x1 / 1x3 / 3x1
+    / 5x5 and the unpadded stride-2 layers of InceptionV3.  rows = (r0, r1): the launch covers the kernel rows r0 .. r1 - 1 only and
+    its weight tensor holds just those rows -- a kernel of more than 16 taps (the tap tables of the conv kernels hold 16) runs as
+    several launches that add up through add1."""
+    (kh, kw), (sh, sw), (ph, pw) = k, s, p
+    OH, OW = (IH + 2 * ph - kh) // sh + 1, (IW + 2 * pw - kw) // sw + 1
+    r0, r1 = rows if rows is not None else (0, kh)
+    return Geom(B, IH, IW, OH, OW, sh, sw, r0 - ph, -pw, 1, 1, r1 - r0, kw, kw, 0, 0, 1, 1, OH, OW, 1, 1, 0, 0)
+
+
 def geom_dgrad_s1(B, H, W, k, p):
     """stride-1 conv with input (H, W): gathers the conv OUTPUT-sized tensor at iy = y + p - ky."""
     GH, GW = H + 2 * p - k + 1, W + 2 * p - k + 1

@@ -11,14 +11,16 @@ Inference only: no gradient flows through them.
 
 FID (metrics.py:17-41, module/piq/fid.py): the statistic -- float64 mean and covariance of a feature set, the Newton-Schulz
 square root of the covariance product with its data-dependent stop, the distance and the reference's singular fallback -- runs
-on the HIP kernels of csrc/fid.hip (fid_statistics / fid_distance64 / compute_FID).  The feature network
-(the reference: piq's InceptionV3 on a downloaded checkpoint) does NOT ship: compute_feat takes it as `extractor`, any callable,
-and it runs in whatever the caller built it from."""
+on the HIP kernels of csrc/fid.hip (fid_statistics / fid_distance64 / compute_FID).  The feature network (the
+reference: piq's InceptionV3 on a downloaded checkpoint) is `InceptionV3Features(state_dict)` (inception.py): the
+checkpoint is the caller's to hand over, the network runs on the HIP kernels.  compute_feat takes it -- or any other callable the
+caller built -- as `extractor`."""
 import numpy as np
 import torch
 
 from . import _lib
 from . import kernels as K
+from .inception import InceptionV3Features  # noqa: F401  -- the public name is metrics.InceptionV3Features
 
 
 def _pair_sums(a, b, clip_a=False):
@@ -355,17 +357,20 @@ def compute_FID(input_feats, target_feats, pred_feats):
 
 @torch.no_grad()
 def compute_feat(input, target, pred, device=None, *, extractor):
-    """metrics.py:17-31 with the feature network handed over: `extractor` is any callable on a (B, 3, H, W) batch -- it runs in
-    whatever the caller built it from, this package ships none (the reference: piq's InceptionV3).  It is applied to
-    x.repeat(1, 3, 1, 1) of each image set and returns a tensor, or a list / tuple of exactly one; the result is flattened to
-    (B, D).  `device` is accepted for the reference's signature; the tensors' device is used."""
+    """metrics.py:17-31 with the feature network handed over: `extractor` is InceptionV3Features(state_dict) (the reference: piq's
+    InceptionV3; the checkpoint is the caller's) or any callable on a (B, 3, H, W) batch, which runs in whatever the caller built
+    it from.  It is applied to x.repeat(1, 3, 1, 1) of each image set -- to x itself where the extractor says
+    `takes_single_channel = True`, as InceptionV3Features does (its first layer is folded to one input channel) -- and returns a
+    tensor, or a list / tuple of exactly one; the result is flattened to (B, D).  `device` is accepted for the reference's
+    signature; the tensors' device is used."""
     if not callable(extractor):
         raise TypeError("compute_feat: pass the feature network as extractor=<callable> (no feature network ships with this package)")
     if not (input.shape == target.shape and target.shape == pred.shape):
         raise AssertionError("compute_feat expects three tensors of the same shape")
+    single = getattr(extractor, "takes_single_channel", False) is True
     feats = []
     for x in (input, target, pred):
-        f = extractor(x.repeat(1, 3, 1, 1))
+        f = extractor(x if single else x.repeat(1, 3, 1, 1))
         if isinstance(f, (list, tuple)):
             if len(f) != 1:
                 raise AssertionError(f"feature_encoder must return list with features from one layer. Got {len(f)}")
