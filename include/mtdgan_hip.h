@@ -510,6 +510,15 @@ int mtd_edge_loss(const float* a, const float* b, int B, float scale, float eps,
  * RMSE = sqrt(out2[0] / n), PSNR = 10 log10(1 / (out2[0] / n + 1e-10)), SSIM = out2[1] / n with n = B*H*W. */
 size_t mtd_image_metrics_ws_bytes(int B, int H, int W);
 int mtd_image_metrics(const float* a, const float* b, int B, int H, int W, int clip_a, double* out2, void* ws, void* stream);
+/* The same sums image by image, for na in 1..3 sources a[k] (B, H, W) against one b: out (na, B, 2) doubles, out[k][i] = the two
+ * sums of image i of (a[k]', b), a[k]' = clip(a[k], 0, 1) if clip_a[k].  One tile launch over na * B images and one finishing launch
+ * (a workgroup per source and image, which sums that image's tile partials in the order of a one-image call): out[k][i] has the
+ * bits of mtd_image_metrics(a[k] + i*H*W, b + i*H*W, 1, H, W, clip_a[k], ...).  a and clip_a are read on the host during the call
+ * (their first na entries).  na * B > 65535, null pointers, non-positive sizes: MTD_EINVAL (the _ws_bytes query then returns 0
+ * for na or a size out of range). */
+size_t mtd_image_metrics_each_ws_bytes(int na, int B, int H, int W);
+int mtd_image_metrics_each(const float* const a[3], int na, const float* b, int B, int H, int W, const int clip_a[3], double* out,
+                           void* ws, void* stream);
 
 /* ---- perceptual metrics of the test loop (metrics.py:43-168: PL and TML on VGG-19 features; engine.py:139-140) ------
  * The convolutions of the feature stack are mtd_conv_* launches; these are the other pieces.  Maps are contiguous NHWC fp32,
@@ -525,6 +534,12 @@ int mtd_image_metrics(const float* a, const float* b, int B, int H, int W, int c
  *                         order (per-workgroup partials in ws, mtd_patch_gram_l1_ws_bytes(B, h, w, C) bytes, then one finishing
  *                         pass), and X, Y run through the same instructions: X == Y gives exactly 0.  No patch (h or w < 16), any
  *                         other C, null pointers: MTD_EINVAL (the _ws_bytes query then returns 0).
+ *   mtd_patch_gram_l1_each  the same sum image by image: out[i * out_stride] = the sum over the patches of image i, i < B
+ *                         (out_stride >= 1 doubles, so that a level writes straight into a (who, image, level) table).  The same
+ *                         kernel and workspace (mtd_patch_gram_l1_ws_bytes); the finishing pass runs a workgroup per image, which
+ *                         walks that image's partials in the order of a one-image call: out[i * out_stride] has the bits of
+ *                         mtd_patch_gram_l1 on image i alone, and X == Y gives exactly 0 for every image.  Shape rules and errors
+ *                         as mtd_patch_gram_l1; out_stride < 1: MTD_EINVAL.
  *   mtd_scaled_sums_f64   out[g] = (float) sum_{i < per} scales_host[i] * in[g * per + i] for g < groups: the weighted sum over
  *                         the five feature levels of several loss values at once.  per <= MTD_SCALED_SUMS_MAX; scales_host is
  *                         read on the host during the call. */
@@ -533,6 +548,8 @@ int mtd_image_metrics(const float* a, const float* b, int B, int H, int W, int c
 int mtd_maxpool2x2(const float* in, float* out, int B, int H, int W, int C, void* stream);
 size_t mtd_patch_gram_l1_ws_bytes(int B, int h, int w, int C);
 int mtd_patch_gram_l1(const float* X, const float* Y, int B, int h, int w, int C, double* out, void* ws, void* stream);
+int mtd_patch_gram_l1_each(const float* X, const float* Y, int B, int h, int w, int C, double* out, long long out_stride, void* ws,
+                           void* stream);
 int mtd_scaled_sums_f64(const double* in, int groups, int per, const double* scales_host, float* out, void* stream);
 
 /* ---- Frechet distance of the test loop (module/piq/fid.py; metrics.py:33-41, engine.py:179-181) -- DESIGN 3.8 -----------

@@ -273,6 +273,9 @@ def lib():
     sig("mtd_edge_loss_ws_bytes", sz, ci)
     sig("mtd_image_metrics_ws_bytes", sz, ci, ci, ci)
     sig("mtd_image_metrics", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
+    sig("mtd_image_metrics_each_ws_bytes", sz, ci, ci, ci, ci)
+    sig("mtd_image_metrics_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, C.POINTER(ci), vp, vp, vp)
+    sig("mtd_patch_gram_l1_each", ci, vp, vp, ci, ci, ci, ci, vp, ll, vp, vp)
     sig("mtd_maxpool2x2", ci, vp, vp, ci, ci, ci, ci, vp)
     sig("mtd_patch_gram_l1_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_patch_gram_l1", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
@@ -354,6 +357,7 @@ EXPORTS = [
     "mtd_maxpool2x2", "mtd_patch_gram_l1_ws_bytes", "mtd_patch_gram_l1", "mtd_scaled_sums_f64",
     "mtd_fid_ws_bytes", "mtd_fid_stats", "mtd_fid_gemm", "mtd_fid_residual", "mtd_fid_distance",
     "mtd_resize_bilinear", "mtd_pool3x3", "mtd_global_avgpool",
+    "mtd_image_metrics_each_ws_bytes", "mtd_image_metrics_each", "mtd_patch_gram_l1_each",
 ]
 
 

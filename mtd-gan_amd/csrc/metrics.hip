@@ -11,14 +11,15 @@ constexpr int MT = 32;            // output tile
 constexpr int MR = 5;             // window radius
 constexpr int MH = MT + 2 * MR;   // 42
 
-__global__ __launch_bounds__(256) void image_metrics_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
-                                                            int clip_a, double* __restrict__ partial) {
+// One 32x32 tile of image `img` (an offset in floats into a and b): its two sums go to part2[0..1].  The body of both tile
+// kernels below, so that a tile gives the same bits whichever of them ran it.
+__device__ __forceinline__ void metrics_tile(const float* __restrict__ a, const float* __restrict__ b, long long img, int H, int W,
+                                             int clip_a, double* __restrict__ part2) {
     __shared__ float As[MH * MH], Bs[MH * MH];
     __shared__ float Hs[5][MH * MT];
     __shared__ double red[2][256];
     const int tid = threadIdx.x;
     const int tx0 = blockIdx.x * MT, ty0 = blockIdx.y * MT;
-    const long long img = (long long)blockIdx.z * H * W;
     float gw[11];
     {
         float s = 0.f;
@@ -84,10 +85,45 @@ __global__ __launch_bounds__(256) void image_metrics_kernel(const float* __restr
         __syncthreads();
     }
     if (tid == 0) {
-        const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[2 * blk] = red[0][0];
-        partial[2 * blk + 1] = red[1][0];
+        part2[0] = red[0][0];
+        part2[1] = red[1][0];
     }
+}
+
+__global__ __launch_bounds__(256) void image_metrics_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
+                                                            int clip_a, double* __restrict__ partial) {
+    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    metrics_tile(a, b, (long long)blockIdx.z * H * W, H, W, clip_a, partial + 2 * blk);
+}
+
+// Up to three sources against one b, image by image: blockIdx.z = source * B + image.  The sources arrive by value.
+struct EachSources { const float* a[3]; int clip[3]; };
+
+__global__ __launch_bounds__(256) void image_metrics_each_kernel(EachSources src, const float* __restrict__ b, int B, int H, int W,
+                                                                 double* __restrict__ partial) {
+    const int k = blockIdx.z / B, i = blockIdx.z - k * B;
+    const float* a = k == 0 ? src.a[0] : (k == 1 ? src.a[1] : src.a[2]);
+    const int clip_a = k == 0 ? src.clip[0] : (k == 1 ? src.clip[1] : src.clip[2]);
+    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    metrics_tile(a, b, (long long)i * H * W, H, W, clip_a, partial + 2 * blk);
+}
+
+// One workgroup per (source, image): the image's `tiles` partials in the order image_metrics_finish_kernel gives a one-image
+// call (thread t takes t, t + 256, ... of the image's own tile numbering, then the same tree), so the sums have its bits.
+__global__ __launch_bounds__(256) void image_metrics_each_finish_kernel(const double* __restrict__ partial, long long tiles,
+                                                                        double* __restrict__ out) {
+    __shared__ double red[2][256];
+    const double* p = partial + 2 * tiles * blockIdx.x;
+    double s0 = 0.0, s1 = 0.0;
+    for (long long i = threadIdx.x; i < tiles; i += 256) { s0 += p[2 * i]; s1 += p[2 * i + 1]; }
+    red[0][threadIdx.x] = s0;
+    red[1][threadIdx.x] = s1;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { out[2 * blockIdx.x] = red[0][0]; out[2 * blockIdx.x + 1] = red[1][0]; }
 }
 
 __global__ __launch_bounds__(256) void image_metrics_finish_kernel(const double* __restrict__ partial, long long nblk, double* __restrict__ out2) {
@@ -120,6 +156,29 @@ extern "C" int mtd_image_metrics(const float* a, const float* b, int B, int H, i
     hipLaunchKernelGGL(image_metrics_kernel, grid, dim3(256), 0, s, a, b, H, W, clip_a, (double*)ws);
     MTD_LAUNCH_CHECK();
     hipLaunchKernelGGL(image_metrics_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, metric_blocks(B, H, W), out2);
+    MTD_LAUNCH_CHECK();
+    return MTD_OK;
+}
+
+extern "C" size_t mtd_image_metrics_each_ws_bytes(int na, int B, int H, int W) {
+    if (na < 1 || na > 3 || B <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)na * (size_t)metric_blocks(B, H, W) * 2 * sizeof(double);
+}
+
+extern "C" int mtd_image_metrics_each(const float* const a[3], int na, const float* b, int B, int H, int W, const int clip_a[3],
+                                      double* out, void* ws, void* stream) {
+    if (!a || !clip_a || !b || !out || !ws || na < 1 || na > 3 || B <= 0 || H <= 0 || W <= 0 || (long long)na * B > 65535) return MTD_EINVAL;
+    EachSources src;
+    for (int k = 0; k < 3; ++k) {
+        src.a[k] = k < na ? a[k] : nullptr;
+        src.clip[k] = k < na ? clip_a[k] : 0;
+        if (k < na && !a[k]) return MTD_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((W + MT - 1) / MT, (H + MT - 1) / MT, na * B);
+    hipLaunchKernelGGL(image_metrics_each_kernel, grid, dim3(256), 0, s, src, b, B, H, W, (double*)ws);
+    MTD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(image_metrics_each_finish_kernel, dim3(na * B), dim3(256), 0, s, (const double*)ws, metric_blocks(1, H, W), (double*)out);
     MTD_LAUNCH_CHECK();
     return MTD_OK;
 }

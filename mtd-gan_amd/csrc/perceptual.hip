@@ -131,6 +131,28 @@ __global__ __launch_bounds__(256) void gram_l1_finish_kernel(const double* __res
     if (threadIdx.x == 0) out[0] = red[0];
 }
 
+// One workgroup per image.  The partials sit at pair * patches + patch with an image's P1 patches contiguous; image i's are
+// walked in the linear order pair * P1 + p of a one-image call (thread = index mod 256, the same tree), so out[i * out_stride]
+// has the bits gram_l1_finish_kernel gives that image alone.
+__global__ __launch_bounds__(256) void gram_l1_each_finish_kernel(const double* __restrict__ partial, long long patches, int P1, int pairs,
+                                                                  double* __restrict__ out, long long out_stride) {
+    __shared__ double red[256];
+    const double* p = partial + (long long)blockIdx.x * P1;
+    const int n1 = pairs * P1;                       // below 2^31: checked by mtd_patch_gram_l1_each
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n1; i += 256) {
+        const int pair = i / P1, q = i - pair * P1;
+        s += p[(long long)pair * patches + q];
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[(long long)blockIdx.x * out_stride] = red[0];
+}
+
 struct Scales { double s[MTD_SCALED_SUMS_MAX]; };
 
 __global__ void scaled_sums_kernel(const double* __restrict__ in, int groups, int per, Scales sc, float* __restrict__ out) {
@@ -177,6 +199,23 @@ extern "C" int mtd_patch_gram_l1(const float* X, const float* Y, int B, int h, i
                        (double*)ws);
     MTD_LAUNCH_CHECK();
     hipLaunchKernelGGL(gram_l1_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, patches * pairs, out);
+    MTD_LAUNCH_CHECK();
+    return MTD_OK;
+}
+
+extern "C" int mtd_patch_gram_l1_each(const float* X, const float* Y, int B, int h, int w, int C, double* out, long long out_stride, void* ws,
+                                      void* stream) {
+    if (!X || !Y || !out || !ws || out_stride < 1 || !gram_shape_ok(B, h, w, C)) return MTD_EINVAL;
+    const long long P1 = gram_patches(1, h, w);
+    const int pairs = gram_pairs(C);
+    if (P1 * pairs >= (1ll << 31)) return MTD_EINVAL;
+    if (!aligned16(X) || !aligned16(Y)) return MTD_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    const long long patches = gram_patches(B, h, w);
+    hipLaunchKernelGGL(patch_gram_l1_kernel, dim3((unsigned)patches, (unsigned)pairs), dim3(256), 0, s, X, Y, h, w, C, h / GP, w / GP,
+                       (double*)ws);
+    MTD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(gram_l1_each_finish_kernel, dim3((unsigned)B), dim3(256), 0, s, (const double*)ws, patches, (int)P1, pairs, out, out_stride);
     MTD_LAUNCH_CHECK();
     return MTD_OK;
 }

@@ -216,6 +216,48 @@ def valid_MTD_GAN_Ours(model, loss, data_loader, device, epoch, save_dir, print_
     return {"L1_loss": round(m.global_avg, 7)}
 
 
+def _l1_each(loss, pred, target):
+    """_l1 of every slice: B device values.  nn.L1Loss's mean is one loss-term launch of B terms, each the one-slice term."""
+    from . import kernels as K
+    B = pred.shape[0]
+    if isinstance(loss, torch.nn.L1Loss) and loss.reduction == "mean":
+        p, t = pred.contiguous(), target.contiguous()
+        return K.loss_terms([K.make_term(1, p[i], t[i], scale=1.0 / p[i].numel()) for i in range(B)], p.device)
+    return torch.stack([torch.as_tensor(loss(pred[i:i + 1], target[i:i + 1]), device=pred.device).reshape(()) for i in range(B)])
+
+
+def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows):
+    """One loader batch of test_MTD_GAN_Ours under `model.test_per_slice`: B meter updates and B rows from one host read."""
+    from . import kernels as K, metrics as M
+    B, _, H, W = x.shape
+    clipped = K.clip01(pred.contiguous())
+    parts = [_l1_each(loss, pred, y).double().flatten(), M.pixel_metrics_each(x, y, clipped).flatten()]
+    if vgg is not None:
+        parts.append(M.perceptual_metrics_per_slice(x, y, clipped, vgg).double().flatten())
+    if fid_features is not None:
+        for rows_, f in zip(feats, M.compute_feat(x, y, clipped, extractor=fid_features)):
+            rows_.append(f.float())
+    vals = torch.cat(parts).tolist()                  # every per-slice value of the batch in one device -> host copy
+    l1 = vals[:B]
+    sums = [[vals[B + (k * B + i) * 2:B + (k * B + i) * 2 + 2] for i in range(B)] for k in range(3)]
+    six = [vals[7 * B + r * B:7 * B + (r + 1) * B] for r in range(6)] if vgg is not None else None
+    pm = M._slice_triples(sums, H * W)
+    paths = batch_data.get("path_n_20") if isinstance(batch_data, dict) else None
+    for i in range(B):
+        meters.setdefault("L1_loss", _Meter()).update(l1[i], 1)
+        perceptual = ()
+        if six is not None:
+            for j, name in enumerate(("pl", "tml")):
+                for k, who in enumerate(("input", "gt", "pred")):
+                    meters.setdefault(f"{who}_{name}", _Meter()).update(six[3 * j + k][i], 1)
+            perceptual = (six[2][i], six[5][i])
+        for name in ("rmse", "psnr", "ssim"):
+            for who, v in zip(("input", "gt", "pred"), pm[name][i]):
+                meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+        path = paths[i] if paths is not None else f"slice_{len(rows)}"
+        rows.append((path,) + perceptual + (pm["rmse"][i][2], pm["psnr"][i][2], pm["ssim"][i][2]))
+
+
 @torch.no_grad()
 def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     """Mirror of engine.py:108-183: whole-slice inference, L1, RMSE / PSNR / SSIM of (input, gt, clipped prediction) per slice,
@@ -231,11 +273,19 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     (metrics.compute_FID: float64 statistics and matrix square root on the HIP kernels, DESIGN 3.8; at least two slices);
     without the attribute (or with None) nothing changes.  Slice sizes as in valid_MTD_GAN_Ours (any 16..512 per side with `model.Generator.allow_any_size = True`; the 128 / 256 / 512 squares with
     binary16 activation storage under `model.Generator.activation_dtype = torch.float16`: predictions and metrics stay fp32;
-    window by window under `model.Generator.sliding_window = dict(...)`)."""
+    window by window under `model.Generator.sliding_window = dict(...)`).
+    A loader batch is ONE sample, as in the reference: the metrics reduce over the whole batch tensor and the CSV gets one row
+    per batch, so the reference's per-slice rows need batches of one slice.  `model.test_per_slice = True` takes a batch of B
+    slices as B samples instead: one generator call, one VGG pass on the 3B images and one feature pass per image
+    set, then per-slice L1, pixel and perceptual values -- the reductions of the batch-of-one loop, bit for bit, on the batch's
+    maps -- in ONE device -> host copy per batch, B meter updates and B CSV rows (`path_n_20[i]`; `slice_{k}` counts slices).
+    Keys, key order, CSV columns and the FID block are unchanged; it composes with the three generator settings above, which end
+    at `Generator(x)`.  Without the attribute (or with a falsy value) nothing changes."""
     from . import metrics as M
     model.Generator.eval()
     vgg = getattr(model, "perceptual_vgg", None)
     fid_features = getattr(model, "fid_features", None)
+    per_slice = bool(getattr(model, "test_per_slice", False))
     feats = ([], [], [])
     meters = {}
     rows = []
@@ -243,6 +293,9 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
         x = batch_data["n_20"].to(device).float()
         y = batch_data["n_100"].to(device).float()
         pred = model.Generator(x)
+        if per_slice:
+            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows)
+            continue
         meters.setdefault("L1_loss", _Meter()).update(float(_l1(loss, pred, y)), 1)
         from . import kernels as K
         clipped = K.clip01(pred.contiguous())

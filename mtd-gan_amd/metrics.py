@@ -14,7 +14,11 @@ square root of the covariance product with its data-dependent stop, the distance
 on the HIP kernels of csrc/fid.hip (fid_statistics / fid_distance64 / compute_FID).  The feature network (the
 reference: piq's InceptionV3 on a downloaded checkpoint) is `InceptionV3Features(state_dict)` (inception.py): the
 checkpoint is the caller's to hand over, the network runs on the HIP kernels.  compute_feat takes it -- or any other callable the
-caller built -- as `extractor`."""
+caller built -- as `extractor`.
+
+Per-slice forms for a batch of B slices taken as B samples (engine.test_MTD_GAN_Ours under `model.test_per_slice`):
+pixel_metrics_each / pixel_metrics_per_slice (`mtd_image_metrics_each`), patch_gram_l1_each (`mtd_patch_gram_l1_each`) and
+perceptual_metrics_per_slice.  Their reductions have the bits of the one-slice calls above."""
 import numpy as np
 import torch
 
@@ -85,6 +89,45 @@ def pixel_metrics(input, target, pred):
     return {k: tuple(v) for k, v in out.items()}
 
 
+def pixel_metrics_each(input, target, pred, clip_pred=False):
+    """The sums of pixel_metrics image by image, without a host read: a (3, B, 2) float64 device tensor, [k][i] = (sum of squared
+    error, sum of the SSIM map) of slice i of (input, target, pred)[k] against slice i of target -- the bits of a one-slice
+    mtd_image_metrics call (mtd_image_metrics_each: two launches for the three pairs of the batch).  `clip_pred`: clip the
+    prediction to [0, 1] on the way in."""
+    for t in (input, target, pred):
+        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
+            raise AssertionError("pixel metrics expect (B,1,H,W) tensors of the same shape")
+        if not t.is_cuda:
+            raise RuntimeError("pixel metrics: HIP path needs CUDA tensors (no CPU fallback)")
+    import ctypes
+    srcs = [t.contiguous().float() for t in (input, target, pred)]
+    B, _, H, W = srcs[1].shape
+    L = _lib.lib()
+    out = torch.empty((3, B, 2), dtype=torch.float64, device=srcs[1].device)
+    ws = K.workspace(L.mtd_image_metrics_each_ws_bytes(3, B, H, W), out.device)
+    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    clips = (ctypes.c_int * 3)(0, 0, 1 if clip_pred else 0)
+    _lib.check(L.mtd_image_metrics_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, clips, out.data_ptr(), ws.data_ptr(), K.stream_ptr()),
+               "mtd_image_metrics_each")
+    return out
+
+
+def _slice_triples(sums, n):
+    """sums: pixel_metrics_each's tensor as nested lists.  dict rmse / psnr / ssim -> list of B (input, gt, pred) triples, by the
+    formulas of pixel_metrics with n = H * W."""
+    B = len(sums[0])
+    return {"rmse": [tuple(float(np.sqrt(np.float32(sums[k][i][0] / n))) for k in range(3)) for i in range(B)],
+            "psnr": [tuple(_psnr(sums[k][i][0], n, 1.0) for k in range(3)) for i in range(B)],
+            "ssim": [tuple(float(np.float32(sums[k][i][1] / n)) for k in range(3)) for i in range(B)]}
+
+
+def pixel_metrics_per_slice(input, target, pred):
+    """pixel_metrics of every slice of a batch: dict rmse / psnr / ssim -> list of B (input, gt, pred) triples, each equal to
+    pixel_metrics(input[i:i+1], target[i:i+1], pred[i:i+1]).  Two launches and one device -> host copy for the batch."""
+    sums = pixel_metrics_each(input, target, pred).tolist()
+    return _slice_triples(sums, target.shape[2] * target.shape[3])
+
+
 # ================================================================================================ perceptual metrics
 # torchvision vgg19().features: index of each conv -> (C_in, C_out); ReLU follows at index + 1
 _VGG19_CONVS = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256), (16, 256, 256),
@@ -116,6 +159,26 @@ def patch_gram_l1(x, y, out=None):
         out = torch.empty(1, dtype=torch.float64, device=x.device)
     ws = K.workspace(max(need, 8), x.device)
     _lib.check(L.mtd_patch_gram_l1(x.data_ptr(), y.data_ptr(), B, h, w, Cc, out.data_ptr(), ws.data_ptr(), K.stream_ptr()), "mtd_patch_gram_l1")
+    return out
+
+
+def patch_gram_l1_each(x, y, out=None, out_stride=1):
+    """patch_gram_l1 image by image: B device doubles, [i] with the bits of patch_gram_l1(x[i:i+1], y[i:i+1])
+    (mtd_patch_gram_l1_each).  With `out`, a float64 tensor (or view) of at least (B - 1) * out_stride + 1 elements, image i's sum
+    goes to its element i * out_stride and nothing else is written."""
+    if x.shape != y.shape or x.dim() != 4 or not (x.is_cuda and y.is_cuda) or not (x.is_contiguous() and y.is_contiguous()):
+        raise ValueError("patch_gram_l1_each: two contiguous CUDA NHWC maps of one shape expected")
+    B, h, w, Cc = x.shape
+    if out_stride < 1:
+        raise ValueError("patch_gram_l1_each: out_stride of at least 1 expected")
+    if out is None:
+        out = torch.empty((B - 1) * out_stride + 1, dtype=torch.float64, device=x.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < (B - 1) * out_stride + 1:
+        raise ValueError("patch_gram_l1_each: `out` must be a contiguous float64 tensor of at least (B - 1) * out_stride + 1 elements")
+    L = _lib.lib()
+    ws = K.workspace(max(L.mtd_patch_gram_l1_ws_bytes(B, h, w, Cc), 8), x.device)
+    _lib.check(L.mtd_patch_gram_l1_each(x.data_ptr(), y.data_ptr(), B, h, w, Cc, out.data_ptr(), out_stride, ws.data_ptr(), K.stream_ptr()),
+               "mtd_patch_gram_l1_each")
     return out
 
 
@@ -281,6 +344,52 @@ def perceptual_metrics(input, target, pred, vgg):
     _perceptual_inputs("perceptual_metrics", input, target, pred, vgg, 16 * TML_PATCH)
     levels = _stacked_features(vgg, target, (input, pred))
     return torch.cat([_pl_values(levels, (1, 0, 2)), _tml_values(levels, (1, 0, 2))])
+
+
+def _pl_each(levels):
+    """PL of every image of the two others against the target: (2, B) floats, one loss_terms call of 2 * 5 * B terms (a term per
+    image and level on the image's slice of the map, scale w_level / (h * w * C): the bits of the one-image term) and one
+    launch for the sums over the levels."""
+    B = levels[0][0].shape[0]
+    terms = []
+    for k in range(2):
+        for i in range(B):
+            for wgt, (ft, fo) in zip(LEVEL_WEIGHTS, levels):
+                terms.append(K.make_term(1, fo[k][i], ft[i], scale=wgt / ft[i].numel()))
+    dev = levels[0][0].device
+    vals = K.loss_terms(terms, dev)
+    return K.scalar_sums([(vals[5 * j:5 * j + 5], None) for j in range(2 * B)], dev).reshape(2, B)
+
+
+def _tml_each(levels):
+    """TML of every image: (3, B) floats, rows input, gt (the constant 0, no launch), pred.  Ten patch_gram_l1_each calls write
+    a (who, image, level) table of doubles, one mtd_scaled_sums_f64 weighs the levels."""
+    import ctypes
+    B = levels[0][0].shape[0]
+    dev = levels[0][0].device
+    sums = torch.zeros(3 * B * 5, dtype=torch.float64, device=dev)
+    scales = (ctypes.c_double * 5)()
+    for lvl, (wgt, (ft, fo)) in enumerate(zip(LEVEL_WEIGHTS, levels)):
+        _, h, w, Cc = ft.shape
+        scales[lvl] = wgt / (float((h // TML_PATCH) * (w // TML_PATCH)) * Cc * Cc)
+        for k, who in enumerate((0, 2)):
+            patch_gram_l1_each(fo[k], ft, out=sums[who * B * 5 + lvl:], out_stride=5)
+    out = torch.empty(3 * B, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().mtd_scaled_sums_f64(sums.data_ptr(), 3 * B, 5, scales, out.data_ptr(), K.stream_ptr()), "mtd_scaled_sums_f64")
+    return out.reshape(3, B)
+
+
+@torch.no_grad()
+def perceptual_metrics_per_slice(input, target, pred, vgg):
+    """perceptual_metrics of every slice of a batch from ONE pass of the network on the 3B stacked images: a (6, B) float32
+    device tensor, rows input_pl, gt_pl, pred_pl, input_tml, gt_tml, pred_tml (the gt rows the constant 0).  The reductions of
+    slice i are those of a one-slice call on slice i of the maps, bit for bit; the maps themselves come from convolutions on 3B
+    images, which may take another plan than on 3."""
+    _perceptual_inputs("perceptual_metrics_per_slice", input, target, pred, vgg, 16 * TML_PATCH)
+    levels = _stacked_features(vgg, target, (input, pred))
+    pl = _pl_each(levels)
+    zero = torch.zeros((1, target.shape[0]), dtype=torch.float32, device=pl.device)
+    return torch.cat([pl[0:1], zero, pl[1:2], _tml_each(levels)])
 
 
 # ================================================================================================ FID
