@@ -624,6 +624,24 @@ int mtd_window_patches(const short* hu_low, const short* hu_full, int n_slices, 
 /* whole slices (valid / test pipelines, Mayo.py:150-157): out[i] = clip((hu[i] - a_min) / (a_max - a_min), 0, 1) */
 int mtd_hu_window(const short* hu, long long n, float a_min, float a_max, float* out, void* stream);
 
+/* ---- greyscale PNG scanlines of the test loop's slices (csrc/png_gray.hip; image_io.py; reference engine.py:157-159) ----
+ * x: n single-channel float32 images (n, H, W), contiguous.  out: (n, H, 1 + W * depth / 8) bytes, every row the PNG filter
+ * byte 0 followed by its W samples -- what zlib takes as it is.  Any H, W >= 1 and any alignment of `out`; every byte of out
+ * is written once and no other byte is touched.  One call covers all n images (three launches at depth 8, one at depth 16; grids capped and strided).
+ *   depth 8  "stretch": what matplotlib's imsave(cmap="gray") gives a float32 image.  vmin / vmax = smallest / largest FINITE
+ *            pixel of the image (two-stage reduction through ws, no atomics); r = float32(double(x) - double(vmin));
+ *            r = float32(double(r) / (double(vmax) - double(vmin))) (the divisor is NOT rounded to float32); t = r * 256 in
+ *            float32, t == 256 -> 255; level = lut[trunc(t)], below 0 -> lut[0], at or above 256 -> lut[255].  vmin == vmax:
+ *            lut[0] everywhere.  A non-finite pixel: 0.  lut: 256 bytes on the device, the caller's (image_io.GRAY_LUT).
+ *   depth 16 "fixed":   v = round-half-even(clamp(x, 0, 1) * 65535) in float32, most significant byte first; a non-finite
+ *            pixel: 0.  lut and ws are not read (may be NULL).
+ * ws: mtd_gray_png_rows_ws_bytes(n, H, W, depth) bytes, 8-byte aligned (0 for depth 16 and for refused shapes).
+ * MTD_EINVAL: null pointers, n, H or W < 1, another depth, n * H * (1 + W * depth / 8) >= 2^31; MTD_EALIGN: x not 4-byte or ws
+ * not 8-byte aligned.  Nothing is launched then.  The library allocates nothing. */
+size_t mtd_gray_png_rows_ws_bytes(int n, int H, int W, int depth);
+int mtd_gray_png_rows(const float* x, int n, int H, int W, int depth, const unsigned char* lut, unsigned char* out, void* ws,
+                      void* stream);
+
 /* ---- sliding-window inference around a patch predictor (csrc/sliding_window.hip; inferers.py) ---------------------------
  * The reference evaluates its patch-trained models with monai's sliding_window_inference (engine.py:345,378,835).  Windows
  * of rh x rw are laid over (B, H, W) single-channel slices: per axis of length `size`, interval iv (1 <= iv <= roi),

@@ -293,6 +293,8 @@ def lib():
     sig("mtd_foreground_bbox", ci, vp, ci, ci, ci, cf, vp, vp)
     sig("mtd_window_patches", ci, vp, vp, ci, ci, ci, vp, vp, ci, cf, cf, ci, vp, vp, vp)
     sig("mtd_hu_window", ci, vp, ll, cf, cf, vp, vp)
+    sig("mtd_gray_png_rows_ws_bytes", sz, ci, ci, ci, ci)
+    sig("mtd_gray_png_rows", ci, vp, ci, ci, ci, ci, vp, vp, vp, vp)
     sig("mtd_prof_mode", ci, ci)
     sig("mtd_spec_mix_zmask_bytes", sz, ci)
     sig("mtd_spec_mix_fwd4", ci, vp, vp, vp, vp, vp, vp, ci, vp)
@@ -358,6 +360,7 @@ EXPORTS = [
     "mtd_fid_ws_bytes", "mtd_fid_stats", "mtd_fid_gemm", "mtd_fid_residual", "mtd_fid_distance",
     "mtd_resize_bilinear", "mtd_pool3x3", "mtd_global_avgpool",
     "mtd_image_metrics_each_ws_bytes", "mtd_image_metrics_each", "mtd_patch_gram_l1_each",
+    "mtd_gray_png_rows_ws_bytes", "mtd_gray_png_rows",
 ]
 
 

@@ -34,3 +34,14 @@ def product(name, default):
 def lab(name, default):
     """A lab switch: the environment's value under MTD_LAB=1, the default otherwise."""
     return os.environ.get(name, default) if LAB else default
+
+
+def thread_budget(default, most=32):
+    """Host threads a pool of this package may start (image_io.PngWriter): not a switch of the package but the process's own
+    budget, as its launcher states it in OMP_NUM_THREADS, MAX_JOBS or CMAKE_BUILD_PARALLEL_LEVEL (first one set, at most
+    `most`), else `default`.  Never os.cpu_count(), which shows the whole machine whatever share of it the process may use."""
+    for name in ("OMP_NUM_THREADS", "MAX_JOBS", "CMAKE_BUILD_PARALLEL_LEVEL"):
+        v = os.environ.get(name, "")
+        if v.isdigit() and int(v) > 0:
+            return min(int(v), most)
+    return default

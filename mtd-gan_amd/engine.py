@@ -258,6 +258,60 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
         rows.append((path,) + perceptual + (pm["rmse"][i][2], pm["psnr"][i][2], pm["ssim"][i][2]))
 
 
+class _PngSink:
+    """`model.test_save_png` of test_MTD_GAN_Ours: per loader batch one scanline launch on the 3B stacked images (x, y and the RAW
+    prediction, as engine.py:157-159 saves them), one asynchronous copy of the bytes into pinned host memory, and -- once the
+    batch's metrics have been read, which the loop waits for anyway -- three writer submits per slice."""
+
+    def __init__(self, save_dir, depth, level, threads):
+        from . import image_io
+        os.makedirs(save_dir, exist_ok=True)
+        self.save_dir, self.depth = save_dir, depth
+        self.writer = image_io.PngWriter(threads, level)
+
+    @classmethod
+    def from_model(cls, model, save_dir):
+        """Absent or falsy -> None; True -> depth 8, zlib level 6, image_io.default_threads(); or a dict of those three."""
+        cfg = getattr(model, "test_save_png", None)
+        if not cfg:
+            return None
+        cfg = {} if cfg is True else cfg
+        if not isinstance(cfg, dict) or set(cfg) - {"depth", "level", "threads"}:
+            raise ValueError(f"model.test_save_png: True or a dict with the keys depth, level, threads; got {cfg!r}")
+        depth = cfg.get("depth", 8)
+        if depth not in (8, 16):
+            raise ValueError(f"model.test_save_png: depth must be 8 or 16, got {depth!r}")
+        if not save_dir:
+            raise ValueError("model.test_save_png is set but test_MTD_GAN_Ours was given no save_dir to write the images to")
+        return cls(save_dir, depth, cfg.get("level", 6), cfg.get("threads"))
+
+    def begin(self, x, y, pred):
+        from . import image_io
+        B, C, H, W = x.shape
+        if C != 1 or y.shape != x.shape or pred.shape != x.shape:
+            raise ValueError(f"test_save_png: expected single-channel x, y and prediction of one shape, got {tuple(x.shape)}, "
+                             f"{tuple(y.shape)}, {tuple(pred.shape)}")
+        rows = image_io.gray_png_rows(torch.cat([x, y, pred]).reshape(3 * B, H, W), self.depth)
+        host = torch.empty(rows.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(rows, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return host, ev, (B, H, W)
+
+    def submit(self, images, batch_data, k0):
+        """k0: slices before this batch (the `slice_{k}` names of batches without paths, counted as the CSV counts)."""
+        from . import image_io
+        host, ev, (B, H, W) = images
+        ev.synchronize()
+        p20 = batch_data.get("path_n_20") if isinstance(batch_data, dict) else None
+        p100 = batch_data.get("path_n_100") if isinstance(batch_data, dict) else None
+        planes = host.numpy()          # (views of the pinned buffer: they keep it alive until the workers are done with it)
+        for i in range(B):
+            names = image_io.png_names(p20[i] if p20 is not None else None, p100[i] if p100 is not None else None, k0 + i)
+            for which, name in enumerate(names):
+                self.writer.submit(os.path.join(self.save_dir, name), planes[which * B + i], H, W, self.depth)
+
+
 @torch.no_grad()
 def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     """Mirror of engine.py:108-183: whole-slice inference, L1, RMSE / PSNR / SSIM of (input, gt, clipped prediction) per slice,
@@ -280,7 +334,25 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     set, then per-slice L1, pixel and perceptual values -- the reductions of the batch-of-one loop, bit for bit, on the batch's
     maps -- in ONE device -> host copy per batch, B meter updates and B CSV rows (`path_n_20[i]`; `slice_{k}` counts slices).
     Keys, key order, CSV columns and the FID block are unchanged; it composes with the three generator settings above, which end
-    at `Generator(x)`.  Without the attribute (or with a falsy value) nothing changes."""
+    at `Generator(x)`.  Without the attribute (or with a falsy value) nothing changes.
+    `model.test_save_png = True` (or `dict(depth=8 | 16, level=..., threads=...)`) writes the reference's three PNGs per slice into
+    save_dir (engine.py:157-159): input, target and the raw prediction are quantised to PNG scanlines on the device in
+    one launch per loader batch, the bytes are copied to the host once, and image_io.PngWriter compresses them on worker threads
+    that are joined before this function returns (a worker's error is raised then).  Greyscale files under the reference's names
+    (image_io.png_names); depth 8 holds imsave's grey levels, depth 16 round(clip(., 0, 1) * 65535) without a stretch.  On the
+    default path a batch of more than one slice is refused (ValueError): the reference's `.squeeze()` has no image for it; use
+    `test_per_slice`, where B slices give 3B files.  Without the attribute (or with a falsy value) nothing changes."""
+    png = _PngSink.from_model(model, save_dir)
+    if png is None:
+        return _test_loop(model, loss, data_loader, device, save_dir, None)
+    try:
+        return _test_loop(model, loss, data_loader, device, save_dir, png)
+    finally:
+        png.writer.close()
+
+
+def _test_loop(model, loss, data_loader, device, save_dir, png):
+    """The body of test_MTD_GAN_Ours; png: the _PngSink of `model.test_save_png`, or None."""
     from . import metrics as M
     model.Generator.eval()
     vgg = getattr(model, "perceptual_vgg", None)
@@ -292,9 +364,16 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     for batch_data in data_loader:
         x = batch_data["n_20"].to(device).float()
         y = batch_data["n_100"].to(device).float()
+        if png is not None and not per_slice and x.shape[0] != 1:
+            raise ValueError(f"test_save_png: a loader batch of {x.shape[0]} slices on the default path, where a batch is one sample "
+                             "and the reference saves its one image; set model.test_per_slice = True for batches of slices")
         pred = model.Generator(x)
+        if png is not None:
+            images, k0 = png.begin(x, y, pred), len(rows)      # one launch and the copy of the bytes, behind the generator
         if per_slice:
             _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows)
+            if png is not None:
+                png.submit(images, batch_data, k0)
             continue
         meters.setdefault("L1_loss", _Meter()).update(float(_l1(loss, pred, y)), 1)
         from . import kernels as K
@@ -315,6 +394,8 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
                 meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
         path = batch_data.get("path_n_20", [f"slice_{len(rows)}"])[0] if isinstance(batch_data, dict) else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]))
+        if png is not None:
+            png.submit(images, batch_data, k0)
     if save_dir:
         import os
         os.makedirs(save_dir, exist_ok=True)

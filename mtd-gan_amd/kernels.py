@@ -1609,6 +1609,19 @@ def clip01_bwd(g, x):
     return out
 
 
+# ------------------------------------------------------------------------------------ PNG scanlines (image_io.py)
+def gray_png_rows(images, depth, lut, out):
+    """(n, H, W) float32 images -> `out`, (n, H, 1 + W * depth / 8) bytes of PNG scanlines with filter byte 0 (mtd_gray_png_rows).
+    lut: the 256 grey levels of depth 8 on the device (not read at depth 16, may be None)."""
+    n, H, W = images.shape
+    L = _lib.lib()
+    nbytes = L.mtd_gray_png_rows_ws_bytes(n, H, W, depth)
+    ws = workspace(nbytes, images.device) if nbytes else None
+    check(L.mtd_gray_png_rows(images.data_ptr(), n, H, W, depth, lut.data_ptr() if lut is not None else None, out.data_ptr(),
+                              ws.data_ptr() if ws is not None else None, stream_ptr()), "mtd_gray_png_rows")
+    return out
+
+
 # ------------------------------------------------------------------------------- sliding-window inference (inferers.py)
 def sw_gather(x, roi, intervals, w0, n, out):
     """Windows [w0, w0 + n) of the (B, 1, H, W) batch x -> out[:n] of the (>= n, 1, rh, rw) buffer `out`."""
