@@ -664,6 +664,27 @@ int mtd_sw_blend(const float* pred, const float* map, int B, int H, int W, int r
                  float* acc, void* stream);
 int mtd_sw_finish(const float* acc, const float* map, int B, int H, int W, int rh, int rw, int ivy, int ivx, int clip01, float* out,
                   void* stream);
+/* Several outputs of one predictor pass (inferers.sliding_window_inference_multi; the reference's module/sliding_window.py runs
+ * its multi-task discriminators this way): 1 <= nplanes <= 4 planes share the geometry, the map and one launch.  preds, scalar,
+ * accs, clip01 and outs are HOST arrays of nplanes entries, read before the launch (the descriptors travel in the kernel
+ * arguments).
+ *   mtd_sw_blend_multi   plane k: accs[k](B, H, W) += map * preds[k] over the windows [w0, w0 + n), as mtd_sw_blend.  scalar[k] == 0:
+ *                        preds[k] is a map (n, rh, rw); scalar[k] != 0: preds[k] is (n) and every pixel of window w contributes
+ *                        preds[k][w].  A pixel's covering windows are found once and walked once for all planes; per plane the
+ *                        operations are mtd_sw_blend's, so accs[k] holds the bits one mtd_sw_blend on that plane (a scalar plane
+ *                        expanded to (n, rh, rw)) would give.
+ *   mtd_sw_finish_multi  plane k: outs[k] = accs[k] / wsum, clipped to [0, 1] if clip01[k]; wsum is computed once per pixel.
+ *                        outs[k] may be accs[k].  The bits of mtd_sw_finish per plane.
+ *   mtd_sw_gather_flags  mtd_sw_gather, and flags[i] = 1 if window w0 + i holds an element != 0.0f (-0.0f is zero, a NaN is
+ *                        not), else 0, for i in [0, n): the call zeroes flags[0, n) on the stream, then every wave that saw a
+ *                        nonzero element stores the constant 1 (plain byte stores, no atomics).
+ * MTD_EINVAL as above, and for nplanes outside 1..4, a null array or a null plane pointer. */
+int mtd_sw_blend_multi(int nplanes, const float* const* preds, const int* scalar, float* const* accs, const float* map, int B, int H,
+                       int W, int rh, int rw, int ivy, int ivx, long long w0, int n, void* stream);
+int mtd_sw_finish_multi(int nplanes, const float* const* accs, const int* clip01, float* const* outs, const float* map, int B, int H,
+                        int W, int rh, int rw, int ivy, int ivx, void* stream);
+int mtd_sw_gather_flags(const float* in, int B, int H, int W, int rh, int rw, int ivy, int ivx, long long w0, int n, float* out,
+                        unsigned char* flags, void* stream);
 
 /* ---- backward of one 32 -> 32 channel 3x3 generator layer in ONE launch (csrc/conv_c32_bwd.hip) ----------------------
  * d: the data gradient exactly as mtd_conv_igemm would take it (it must be a launch of the halo-tile kernel: C == N == 32,

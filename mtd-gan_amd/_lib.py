@@ -330,6 +330,9 @@ def lib():
     sig("mtd_sw_gather", ci, vp, ci, ci, ci, ci, ci, ci, ci, ll, ci, vp, vp)
     sig("mtd_sw_blend", ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, ll, ci, vp, vp)
     sig("mtd_sw_finish", ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp)
+    sig("mtd_sw_blend_multi", ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ll, ci, vp)
+    sig("mtd_sw_finish_multi", ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp)
+    sig("mtd_sw_gather_flags", ci, vp, ci, ci, ci, ci, ci, ci, ci, ll, ci, vp, vp, vp)
     _lib = L
     return L
 
@@ -355,7 +358,7 @@ EXPORTS = [
     "mtd_set_option", "mtd_get_option", "mtd_lab_build",
     "mtd_winograd_s2_kmap", "mtd_winograd_s2_weights", "mtd_conv_winograd_s2_ok", "mtd_conv_winograd_s2_ws_bytes", "mtd_conv_winograd_s2",
     "mtd_conv_winograd_st", "mtd_conv_direct_st", "mtd_rfft_rows_any_h", "mtd_spec_mix_any_h", "mtd_irfft_rows_any_h",
-    "mtd_sw_gather", "mtd_sw_blend", "mtd_sw_finish",
+    "mtd_sw_gather", "mtd_sw_blend", "mtd_sw_finish", "mtd_sw_blend_multi", "mtd_sw_finish_multi", "mtd_sw_gather_flags",
     "mtd_maxpool2x2", "mtd_patch_gram_l1_ws_bytes", "mtd_patch_gram_l1", "mtd_scaled_sums_f64",
     "mtd_fid_ws_bytes", "mtd_fid_stats", "mtd_fid_gemm", "mtd_fid_residual", "mtd_fid_distance",
     "mtd_resize_bilinear", "mtd_pool3x3", "mtd_global_avgpool",

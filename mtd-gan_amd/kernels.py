@@ -1646,6 +1646,44 @@ def sw_finish(acc, imap, roi, intervals, clip=False, out=None):
     return out
 
 
+SW_MAX_PLANES = 4
+
+
+def _sw_plane_arrays(who, ptrs, flags):
+    n = len(ptrs[0])
+    if not 1 <= n <= SW_MAX_PLANES or any(len(p) != n for p in ptrs) or len(flags) != n:
+        raise ValueError(f"{who}: 1 to {SW_MAX_PLANES} planes, one entry of every list per plane, got {[len(p) for p in ptrs]} and "
+                         f"{len(flags)} flags")
+    return n, [(C.c_void_p * n)(*[t.data_ptr() for t in p]) for p in ptrs], (C.c_int * n)(*[1 if f else 0 for f in flags])
+
+
+def sw_blend_multi(preds, scalar, imap, accs, roi, intervals, w0, n):
+    """Plane k: accs[k] (B, 1, H, W) += importance map * preds[k] of the windows [w0, w0 + n), all planes in one launch;
+    scalar[k] false: preds[k] is (n, 1, rh, rw), true: preds[k] is (n,) and fills its window.  Per plane the bits of sw_blend."""
+    np_, (pp, pa), sc = _sw_plane_arrays("sw_blend_multi", (preds, accs), scalar)
+    B, _, H, W = accs[0].shape
+    check(_lib.lib().mtd_sw_blend_multi(np_, pp, sc, pa, imap.data_ptr(), B, H, W, roi[0], roi[1], intervals[0], intervals[1], w0, n,
+                                        stream_ptr()), "mtd_sw_blend_multi")
+
+
+def sw_finish_multi(accs, imap, roi, intervals, clips, outs=None):
+    """Plane k: accs[k] / (summed importance of the covering windows), clipped to [0, 1] if clips[k]; one launch, the summed
+    importance computed once per pixel.  In place unless `outs` is given."""
+    outs = accs if outs is None else outs
+    np_, (pa, po), cl = _sw_plane_arrays("sw_finish_multi", (accs, outs), clips)
+    B, _, H, W = accs[0].shape
+    check(_lib.lib().mtd_sw_finish_multi(np_, pa, cl, po, imap.data_ptr(), B, H, W, roi[0], roi[1], intervals[0], intervals[1],
+                                         stream_ptr()), "mtd_sw_finish_multi")
+    return outs
+
+
+def sw_gather_flags(x, roi, intervals, w0, n, out, flags):
+    """sw_gather, and flags[i] (uint8, >= n entries) = 1 if window w0 + i holds an element != 0, else 0, for i < n."""
+    B, _, H, W = x.shape
+    check(_lib.lib().mtd_sw_gather_flags(x.data_ptr(), B, H, W, roi[0], roi[1], intervals[0], intervals[1], w0, n, out.data_ptr(),
+                                         flags.data_ptr(), stream_ptr()), "mtd_sw_gather_flags")
+
+
 def edge_loss(a, b, scale, eps=1e-3, grad_out=None, coef=0.0, accumulate=False):
     """a, b: (B,64,64,1) contiguous.  Returns a 1-element tensor scale * sum sqrt(lap(a-b)^2+eps^2)."""
     L = _lib.lib()
