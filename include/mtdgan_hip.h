@@ -642,6 +642,32 @@ size_t mtd_gray_png_rows_ws_bytes(int n, int H, int W, int depth);
 int mtd_gray_png_rows(const float* x, int n, int H, int W, int depth, const unsigned char* lut, unsigned char* out, void* ws,
                       void* stream);
 
+/* ---- stored DICOM pixel values <-> Hounsfield units <-> window (csrc/dicom_domain.hip; dicom_io.py) ----------
+ * The reference's get_pixels_hu (create_datasets/Mayo.py:19-43) and dicom_denormalize + save_dicom (utils.py:167-194), per pixel,
+ * in their own operations.  The arrays are (S, H, W), contiguous, and taken as one run of S H W elements, S H W < 2^31; the
+ * pointers need only their element's alignment (16-byte accesses where the phase allows, scalar head and tail).  rescale:
+ * S pairs of doubles (slope, intercept) on the device, slice s at rescale[2 s].  One launch each; every output element is
+ * written once and nothing else is touched.  No workspace, no allocation, no synchronisation.
+ *   mtd_stored_to_hu      p = the word as int16 (a uint16 array is reinterpreted, 63536 = -2000); p == -2000 -> 0;
+ *                         if slope != 1: p = (int16) trunc(slope * (double) p); hu = p + (int16) trunc(intercept), 16-bit wrap-around.
+ *   mtd_stored_to_window  the same HU, then out = clip(((float) hu - a_min) / (a_max - a_min), 0, 1): bit for bit what mtd_hu_window
+ *                         gives on mtd_stored_to_hu's output.  hu_out (may be NULL): the int16 HU as well.
+ *   mtd_window_to_stored  v is clipped to [0, 1] if clip; hu = (a_max - a_min) * v, then + a_min (fp32, two roundings);
+ *                         t = hu - (float) intercept; s = (int16) trunc(t); if slope != 1: s = (int16) trunc((float) s / (float) slope).
+ *                         rounding 0: both casts truncate toward zero (the reference); 1: both round to nearest, ties to even.
+ *                         outside 0: nothing more (the reference); 1: where the HU of ref_stored's word (mtd_stored_to_hu's
+ *                         arithmetic, same rescale) lies outside [a_min, a_max], that word is written instead.  ref_stored is
+ *                         read only then (may be NULL otherwise) and must not overlap out.
+ * Every cast to int16 SATURATES (below -32768 -> -32768, above 32767 -> 32767, NaN -> 0): the reference's numpy casts are defined
+ * only for values inside the range, where both agree.
+ * MTD_EINVAL: null pointers, S, H or W < 1, S H W >= 2^31, a_max <= a_min, rounding or outside not 0 / 1, outside 1 without
+ * ref_stored; MTD_EALIGN: a pointer short of its element's alignment (2 / 4 / 8 bytes).  Nothing is launched then. */
+int mtd_stored_to_hu(const short* stored, int S, int H, int W, const double* rescale, short* hu_out, void* stream);
+int mtd_stored_to_window(const short* stored, int S, int H, int W, const double* rescale, float a_min, float a_max, float* out,
+                         short* hu_out, void* stream);
+int mtd_window_to_stored(const float* v, int S, int H, int W, const double* rescale, float a_min, float a_max, int clip, int rounding,
+                         int outside, const short* ref_stored, short* out, void* stream);
+
 /* ---- sliding-window inference around a patch predictor (csrc/sliding_window.hip; inferers.py) ---------------------------
  * The reference evaluates its patch-trained models with monai's sliding_window_inference (engine.py:345,378,835).  Windows
  * of rh x rw are laid over (B, H, W) single-channel slices: per axis of length `size`, interval iv (1 <= iv <= roi),

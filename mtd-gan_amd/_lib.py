@@ -295,6 +295,9 @@ def lib():
     sig("mtd_hu_window", ci, vp, ll, cf, cf, vp, vp)
     sig("mtd_gray_png_rows_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_gray_png_rows", ci, vp, ci, ci, ci, ci, vp, vp, vp, vp)
+    sig("mtd_stored_to_hu", ci, vp, ci, ci, ci, vp, vp, vp)
+    sig("mtd_stored_to_window", ci, vp, ci, ci, ci, vp, cf, cf, vp, vp, vp)
+    sig("mtd_window_to_stored", ci, vp, ci, ci, ci, vp, cf, cf, ci, ci, ci, vp, vp, vp)
     sig("mtd_prof_mode", ci, ci)
     sig("mtd_spec_mix_zmask_bytes", sz, ci)
     sig("mtd_spec_mix_fwd4", ci, vp, vp, vp, vp, vp, vp, ci, vp)
@@ -364,6 +367,7 @@ EXPORTS = [
     "mtd_resize_bilinear", "mtd_pool3x3", "mtd_global_avgpool",
     "mtd_image_metrics_each_ws_bytes", "mtd_image_metrics_each", "mtd_patch_gram_l1_each",
     "mtd_gray_png_rows_ws_bytes", "mtd_gray_png_rows",
+    "mtd_stored_to_hu", "mtd_stored_to_window", "mtd_window_to_stored",
 ]
 
 

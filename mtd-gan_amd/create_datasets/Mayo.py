@@ -2,8 +2,9 @@
 HU window [-160, 240] -> [0, 1], crop to the full-dose foreground, pad to >= 64, 8 random 64 x 64 samples per slice, then per
 sample RandRotate90d / RandFlipd / RandRotated (prob 0.1 each).  The reference builds this from monai 1.3.2 transforms on the
 CPU; here one HIP gather (include/mtdgan_hip.h: mtd_foreground_bbox, mtd_window_patches) produces the batch from HU slices
-that are already resident in HBM.  DICOM decoding (pydicom, Mayo.py:19-43) stays on the host: get_pixels_hu's int16 HU
-arrays are this module's input.  No CPU fallback."""
+that are already resident in HBM.  Reading the DICOM files (pydicom, Mayo.py:19-43) stays on the host; get_pixels_hu's int16 HU
+arrays are this module's input, either computed there or on the device from the files' stored pixel values by
+dicom_io.stored_to_hu (the same integers), which feeds window_patches and window_slices unchanged.  No CPU fallback."""
 import ctypes as C
 import math
 

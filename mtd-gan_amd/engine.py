@@ -312,6 +312,84 @@ class _PngSink:
                 self.writer.submit(os.path.join(self.save_dir, name), planes[which * B + i], H, W, self.depth)
 
 
+class _StoredInput:
+    """`model.test_from_stored` of test_MTD_GAN_Ours: the loader's batches hold the stored pixel values of the DICOM files and one
+    (slope, intercept) pair per slice, and one fused launch per dose level windows them (dicom_io.stored_to_window)."""
+
+    def __init__(self, a_min, a_max):
+        self.a_min, self.a_max = a_min, a_max
+
+    @classmethod
+    def from_model(cls, model):
+        """Absent or falsy -> None; True -> the training window [-160, 240]; or a dict with a_min and / or a_max."""
+        from . import dicom_io
+        cfg = getattr(model, "test_from_stored", None)
+        if not cfg:
+            return None
+        cfg = {} if cfg is True else cfg
+        if not isinstance(cfg, dict) or set(cfg) - {"a_min", "a_max"}:
+            raise ValueError(f"model.test_from_stored: True or a dict with the keys a_min, a_max; got {cfg!r}")
+        a_min, a_max = float(cfg.get("a_min", dicom_io.A_MIN)), float(cfg.get("a_max", dicom_io.A_MAX))
+        if not a_max > a_min:
+            raise ValueError(f"model.test_from_stored: a_max must exceed a_min, got {a_min!r}, {a_max!r}")
+        return cls(a_min, a_max)
+
+    def window(self, batch_data, key, device):
+        """-> (windowed float32 (B, 1, H, W), the stored words on the device, their (B, 2) rescale table on the device)"""
+        from . import dicom_io
+        name = "rescale_" + key
+        if not isinstance(batch_data, dict) or name not in batch_data:
+            raise ValueError(f"model.test_from_stored: the batch carries no '{name}', the (B, 2) (slope, intercept) pairs of '{key}'")
+        words = batch_data[key]
+        if not isinstance(words, torch.Tensor) or words.dtype not in (torch.int16, torch.uint16) or words.dim() != 4 or words.shape[1] != 1:
+            raise ValueError(f"model.test_from_stored: batch['{key}'] must be an int16 or uint16 tensor (B, 1, H, W) of stored pixel "
+                             f"values, got {getattr(words, 'dtype', type(words))} {tuple(getattr(words, 'shape', ()))}")
+        words = words.to(device).contiguous()
+        table = dicom_io.rescale_table(batch_data[name], words.shape[0], words.device)
+        return dicom_io.stored_to_window(words, table, self.a_min, self.a_max), words, table
+
+
+class _DcmSink:
+    """`model.test_save_dcm` of test_MTD_GAN_Ours: per loader batch one launch takes the RAW prediction back to stored pixel
+    values (dicom_io.window_to_stored: clipped, the reference's truncation, the input's own word where the input lies outside
+    the window), one asynchronous copy brings the int16 slices to pinned host memory, and -- once the batch's metrics have been
+    read -- the callable gets one call per slice."""
+
+    def __init__(self, write, stored):
+        self.write, self.stored = write, stored
+
+    @classmethod
+    def from_model(cls, model, stored):
+        """Absent or falsy -> None; else a callable(path_n_20, stored_int16_2d_numpy, k).  stored: the _StoredInput, or None."""
+        cfg = getattr(model, "test_save_dcm", None)
+        if not cfg:
+            return None
+        if not callable(cfg):
+            raise ValueError(f"model.test_save_dcm: a callable(path_n_20, stored_int16_2d, k), e.g. dicom_io.pydicom_writer(dcm_dir); got {cfg!r}")
+        if stored is None:
+            raise ValueError("model.test_save_dcm needs model.test_from_stored: the way back to stored pixel values takes the "
+                             "(slope, intercept) pairs and the stored input of every slice")
+        return cls(cfg, stored)
+
+    def begin(self, pred, words, table):
+        from . import dicom_io
+        out = dicom_io.window_to_stored(pred.float(), table, self.stored.a_min, self.stored.a_max, clip=True, rounding="trunc",
+                                        outside="input", reference=words)
+        host = torch.empty(out.shape, dtype=torch.int16, pin_memory=True)
+        host.copy_(out, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return host, ev
+
+    def submit(self, slices, batch_data, k0):
+        host, ev = slices
+        ev.synchronize()
+        paths = batch_data.get("path_n_20") if isinstance(batch_data, dict) else None
+        planes = host.numpy()
+        for i in range(planes.shape[0]):
+            self.write(paths[i] if paths is not None else None, planes[i, 0], k0 + i)
+
+
 @torch.no_grad()
 def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     """Mirror of engine.py:108-183: whole-slice inference, L1, RMSE / PSNR / SSIM of (input, gt, clipped prediction) per slice,
@@ -341,18 +419,31 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     that are joined before this function returns (a worker's error is raised then).  Greyscale files under the reference's names
     (image_io.png_names); depth 8 holds imsave's grey levels, depth 16 round(clip(., 0, 1) * 65535) without a stretch.  On the
     default path a batch of more than one slice is refused (ValueError): the reference's `.squeeze()` has no image for it; use
-    `test_per_slice`, where B slices give 3B files.  Without the attribute (or with a falsy value) nothing changes."""
+    `test_per_slice`, where B slices give 3B files.  Without the attribute (or with a falsy value) nothing changes.
+    `model.test_from_stored = True` (or `dict(a_min=..., a_max=...)`) reads the loader's batches as the DICOM files'
+    stored pixel values: `n_20` / `n_100` are int16 or uint16 (B, 1, H, W), `rescale_n_20` / `rescale_n_100` their (B, 2)
+    (RescaleSlope, RescaleIntercept) pairs, and one fused launch per dose level (dicom_io.stored_to_window: the reference's
+    get_pixels_hu and the window [-160, 240], or the dict's) replaces `.float()`; everything after it sees the floats that
+    window_slices gives on get_pixels_hu's HU.  `model.test_save_dcm = callable(path_n_20, stored_int16_2d_numpy, k)` (for
+    instance dicom_io.pydicom_writer(dcm_dir), which fills the reference's /dcm/ folder) is called once per slice with the
+    prediction back in stored pixel values (dicom_io.window_to_stored of the raw prediction: clipped, the reference's truncation,
+    the input's own word where the input's HU lies outside the window): one launch and one device -> host copy per loader batch,
+    read after the batch's metrics.  It needs `test_from_stored`, and like the PNGs `test_per_slice` for batches of more than one
+    slice (ValueError otherwise).  Without the attributes (or with falsy values) nothing changes."""
+    stored = _StoredInput.from_model(model)
+    dcm = _DcmSink.from_model(model, stored)
     png = _PngSink.from_model(model, save_dir)
     if png is None:
-        return _test_loop(model, loss, data_loader, device, save_dir, None)
+        return _test_loop(model, loss, data_loader, device, save_dir, None, stored, dcm)
     try:
-        return _test_loop(model, loss, data_loader, device, save_dir, png)
+        return _test_loop(model, loss, data_loader, device, save_dir, png, stored, dcm)
     finally:
         png.writer.close()
 
 
-def _test_loop(model, loss, data_loader, device, save_dir, png):
-    """The body of test_MTD_GAN_Ours; png: the _PngSink of `model.test_save_png`, or None."""
+def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm=None):
+    """The body of test_MTD_GAN_Ours; png: the _PngSink of `model.test_save_png`, stored: the _StoredInput of
+    `model.test_from_stored`, dcm: the _DcmSink of `model.test_save_dcm`, or None each."""
     from . import metrics as M
     model.Generator.eval()
     vgg = getattr(model, "perceptual_vgg", None)
@@ -362,18 +453,30 @@ def _test_loop(model, loss, data_loader, device, save_dir, png):
     meters = {}
     rows = []
     for batch_data in data_loader:
-        x = batch_data["n_20"].to(device).float()
-        y = batch_data["n_100"].to(device).float()
+        if dcm is not None and not per_slice and len(batch_data["n_20"]) != 1:         # (before anything is launched)
+            raise ValueError(f"test_save_dcm: a loader batch of {len(batch_data['n_20'])} slices on the default path, where a batch is "
+                             "one sample; set model.test_per_slice = True for batches of slices")
+        if stored is not None:
+            x, words, table = stored.window(batch_data, "n_20", device)
+            y = stored.window(batch_data, "n_100", device)[0]
+        else:
+            x = batch_data["n_20"].to(device).float()
+            y = batch_data["n_100"].to(device).float()
         if png is not None and not per_slice and x.shape[0] != 1:
             raise ValueError(f"test_save_png: a loader batch of {x.shape[0]} slices on the default path, where a batch is one sample "
                              "and the reference saves its one image; set model.test_per_slice = True for batches of slices")
         pred = model.Generator(x)
+        k0 = len(rows)
         if png is not None:
-            images, k0 = png.begin(x, y, pred), len(rows)      # one launch and the copy of the bytes, behind the generator
+            images = png.begin(x, y, pred)                     # one launch and the copy of the bytes, behind the generator
+        if dcm is not None:
+            slices = dcm.begin(pred, words, table)             # likewise
         if per_slice:
             _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows)
             if png is not None:
                 png.submit(images, batch_data, k0)
+            if dcm is not None:
+                dcm.submit(slices, batch_data, k0)
             continue
         meters.setdefault("L1_loss", _Meter()).update(float(_l1(loss, pred, y)), 1)
         from . import kernels as K
@@ -396,6 +499,8 @@ def _test_loop(model, loss, data_loader, device, save_dir, png):
         rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]))
         if png is not None:
             png.submit(images, batch_data, k0)
+        if dcm is not None:
+            dcm.submit(slices, batch_data, k0)
     if save_dir:
         import os
         os.makedirs(save_dir, exist_ok=True)
