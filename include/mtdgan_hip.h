@@ -512,8 +512,9 @@ size_t mtd_image_metrics_ws_bytes(int B, int H, int W);
 int mtd_image_metrics(const float* a, const float* b, int B, int H, int W, int clip_a, double* out2, void* ws, void* stream);
 /* The same sums image by image, for na in 1..3 sources a[k] (B, H, W) against one b: out (na, B, 2) doubles, out[k][i] = the two
  * sums of image i of (a[k]', b), a[k]' = clip(a[k], 0, 1) if clip_a[k].  One tile launch over na * B images and one finishing launch
- * (a workgroup per source and image, which sums that image's tile partials in the order of a one-image call): out[k][i] has the
- * bits of mtd_image_metrics(a[k] + i*H*W, b + i*H*W, 1, H, W, clip_a[k], ...).  a and clip_a are read on the host during the call
+ * (a workgroup per source and image, which sums that image's tile partials).  mtd_image_metrics runs the same two kernels with
+ * one source and the batch as one group of the finish, so out[k][i] has the bits of
+ * mtd_image_metrics(a[k] + i*H*W, b + i*H*W, 1, H, W, clip_a[k], ...).  a and clip_a are read on the host during the call
  * (their first na entries).  na * B > 65535, null pointers, non-positive sizes: MTD_EINVAL (the _ws_bytes query then returns 0
  * for na or a size out of range). */
 size_t mtd_image_metrics_each_ws_bytes(int na, int B, int H, int W);

@@ -164,6 +164,31 @@ __device__ __forceinline__ f32x4 block_slab_sum(const float* __restrict__ in, lo
     return s;
 }
 
+// Fixed-order sums of N values over the 256 threads of a workgroup: v[k] <- sum over the threads of their v[k], each by the
+// same halving tree (the N sums share its barriers and nothing else); `red` holds N * 256 doubles.  The results are valid in
+// thread 0.
+template <int N>
+__device__ __forceinline__ void block_sum256(double (&v)[N], double* red) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < N; ++k) red[k * 256 + t] = v[k];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) red[k * 256 + t] += red[k * 256 + t + s];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = red[k * 256];
+}
+__device__ __forceinline__ double block_sum256(double v, double* red) {
+    double a[1] = {v};
+    block_sum256(a, red);
+    return a[0];
+}
+
 // launch profiler hooks (api.hip).  Between mtd_prof_begin and mtd_prof_end the main kernel is launched with MTD_LAUNCH:
 // when the profiler is on (kernel-timestamp mode) the slot's two events travel on the kernel's dispatch packet.
 int mtd_prof_begin(int kernel, int cfg, int splitk, long long M, int N, int C, int taps, hipStream_t s, double bytes = 0.0);

@@ -69,17 +69,6 @@ inline FidWs fid_carve(void* ws, int D) {
     return w;
 }
 
-// fixed-order sum over the 256 threads of a workgroup; the result is valid in thread 0
-__device__ __forceinline__ double block_sum256(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 struct MmaArgs {
     const double* A;         // OP_MAT: left factor
     const double* B;         // OP_MAT: right factor

@@ -11,13 +11,21 @@ constexpr int MT = 32;            // output tile
 constexpr int MR = 5;             // window radius
 constexpr int MH = MT + 2 * MR;   // 42
 
-// One 32x32 tile of image `img` (an offset in floats into a and b): its two sums go to part2[0..1].  The body of both tile
-// kernels below, so that a tile gives the same bits whichever of them ran it.
-__device__ __forceinline__ void metrics_tile(const float* __restrict__ a, const float* __restrict__ b, long long img, int H, int W,
-                                             int clip_a, double* __restrict__ part2) {
+// Up to three sources against one b, image by image: blockIdx.z = source * B + image.  The sources arrive by value (the
+// selects below keep them in scalar registers).  One 32x32 tile per workgroup; its two sums go to partial[2 blk], blk the
+// linear workgroup index, so a source's partials are contiguous, image after image.
+struct EachSources { const float* a[3]; int clip[3]; };
+
+__global__ __launch_bounds__(256) void image_metrics_each_kernel(EachSources src, const float* __restrict__ b, int B, int H, int W,
+                                                                 double* __restrict__ partial) {
     __shared__ float As[MH * MH], Bs[MH * MH];
     __shared__ float Hs[5][MH * MT];
-    __shared__ double red[2][256];
+    __shared__ double red[2 * 256];
+    const int si = blockIdx.z / B, i = blockIdx.z - si * B;
+    const float* __restrict__ a = si == 0 ? src.a[0] : (si == 1 ? src.a[1] : src.a[2]);
+    const int clip_a = si == 0 ? src.clip[0] : (si == 1 ? src.clip[1] : src.clip[2]);
+    const long long img = (long long)i * H * W;
+    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     const int tid = threadIdx.x;
     const int tx0 = blockIdx.x * MT, ty0 = blockIdx.y * MT;
     float gw[11];
@@ -58,6 +66,8 @@ __device__ __forceinline__ void metrics_tile(const float* __restrict__ a, const 
         for (int q = 0; q < 5; ++q) Hs[q][e] = m[q];
     }
     __syncthreads();
+    // Two scalars, not an array: which products of the SSIM expression below the compiler fuses into fmas follows how it
+    // vectorises this loop, and with the sums in an array it chooses otherwise (the SSIM sum then moves by 1e-8 of itself).
     double sse = 0.0, ssum = 0.0;
     for (int e = tid; e < MT * MT; e += 256) {
         const int ly = e / MT, lx = e - ly * MT;
@@ -77,70 +87,38 @@ __device__ __forceinline__ void metrics_tile(const float* __restrict__ a, const 
             sse += (double)d * (double)d;
         }
     }
-    red[0][tid] = sse;
-    red[1][tid] = ssum;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; }
-        __syncthreads();
-    }
+    double sums[2] = {sse, ssum};
+    block_sum256(sums, red);
     if (tid == 0) {
-        part2[0] = red[0][0];
-        part2[1] = red[1][0];
+        partial[2 * blk] = sums[0];
+        partial[2 * blk + 1] = sums[1];
     }
 }
 
-__global__ __launch_bounds__(256) void image_metrics_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
-                                                            int clip_a, double* __restrict__ partial) {
-    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    metrics_tile(a, b, (long long)blockIdx.z * H * W, H, W, clip_a, partial + 2 * blk);
-}
-
-// Up to three sources against one b, image by image: blockIdx.z = source * B + image.  The sources arrive by value.
-struct EachSources { const float* a[3]; int clip[3]; };
-
-__global__ __launch_bounds__(256) void image_metrics_each_kernel(EachSources src, const float* __restrict__ b, int B, int H, int W,
-                                                                 double* __restrict__ partial) {
-    const int k = blockIdx.z / B, i = blockIdx.z - k * B;
-    const float* a = k == 0 ? src.a[0] : (k == 1 ? src.a[1] : src.a[2]);
-    const int clip_a = k == 0 ? src.clip[0] : (k == 1 ? src.clip[1] : src.clip[2]);
-    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    metrics_tile(a, b, (long long)i * H * W, H, W, clip_a, partial + 2 * blk);
-}
-
-// One workgroup per (source, image): the image's `tiles` partials in the order image_metrics_finish_kernel gives a one-image
-// call (thread t takes t, t + 256, ... of the image's own tile numbering, then the same tree), so the sums have its bits.
-__global__ __launch_bounds__(256) void image_metrics_each_finish_kernel(const double* __restrict__ partial, long long tiles,
-                                                                        double* __restrict__ out) {
-    __shared__ double red[2][256];
-    const double* p = partial + 2 * tiles * blockIdx.x;
-    double s0 = 0.0, s1 = 0.0;
-    for (long long i = threadIdx.x; i < tiles; i += 256) { s0 += p[2 * i]; s1 += p[2 * i + 1]; }
-    red[0][threadIdx.x] = s0;
-    red[1][threadIdx.x] = s1;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out[2 * blockIdx.x] = red[0][0]; out[2 * blockIdx.x + 1] = red[1][0]; }
-}
-
-__global__ __launch_bounds__(256) void image_metrics_finish_kernel(const double* __restrict__ partial, long long nblk, double* __restrict__ out2) {
-    __shared__ double red[2][256];
-    double s0 = 0.0, s1 = 0.0;
-    for (long long i = threadIdx.x; i < nblk; i += 256) { s0 += partial[2 * i]; s1 += partial[2 * i + 1]; }
-    red[0][threadIdx.x] = s0;
-    red[1][threadIdx.x] = s1;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out2[0] = red[0][0]; out2[1] = red[1][0]; }
+// One workgroup per group of `per_group` consecutive partials (gridDim.x groups): thread t takes t, t + 256, ... of the group's
+// own numbering, then the tree.  A group is one (source, image) for mtd_image_metrics_each and the whole batch for
+// mtd_image_metrics, so an image alone in a batch gets the same sums from either.
+__global__ __launch_bounds__(256) void image_metrics_finish_kernel(const double* __restrict__ partial, long long per_group,
+                                                                   double* __restrict__ out) {
+    __shared__ double red[2 * 256];
+    const double* p = partial + 2 * per_group * blockIdx.x;
+    double sums[2] = {0.0, 0.0};
+    for (long long i = threadIdx.x; i < per_group; i += 256) { sums[0] += p[2 * i]; sums[1] += p[2 * i + 1]; }
+    block_sum256(sums, red);
+    if (threadIdx.x == 0) { out[2 * blockIdx.x] = sums[0]; out[2 * blockIdx.x + 1] = sums[1]; }
 }
 
 long long metric_blocks(int B, int H, int W) { return (long long)B * ((H + MT - 1) / MT) * ((W + MT - 1) / MT); }
+
+// tiles of `na` sources x B images, then their partials summed in `groups` equal groups: out (groups, 2)
+int metrics_launch(const EachSources& src, int na, const float* b, int B, int H, int W, int groups, double* out, void* ws, hipStream_t s) {
+    const dim3 grid((W + MT - 1) / MT, (H + MT - 1) / MT, na * B);
+    hipLaunchKernelGGL(image_metrics_each_kernel, grid, dim3(256), 0, s, src, b, B, H, W, (double*)ws);
+    MTD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(image_metrics_finish_kernel, dim3(groups), dim3(256), 0, s, (const double*)ws, metric_blocks(na * B, H, W) / groups, out);
+    MTD_LAUNCH_CHECK();
+    return MTD_OK;
+}
 
 }  // namespace
 
@@ -151,13 +129,8 @@ extern "C" size_t mtd_image_metrics_ws_bytes(int B, int H, int W) {
 
 extern "C" int mtd_image_metrics(const float* a, const float* b, int B, int H, int W, int clip_a, double* out2, void* ws, void* stream) {
     if (!a || !b || !out2 || !ws || B <= 0 || H <= 0 || W <= 0 || B > 65535) return MTD_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((W + MT - 1) / MT, (H + MT - 1) / MT, B);
-    hipLaunchKernelGGL(image_metrics_kernel, grid, dim3(256), 0, s, a, b, H, W, clip_a, (double*)ws);
-    MTD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(image_metrics_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, metric_blocks(B, H, W), out2);
-    MTD_LAUNCH_CHECK();
-    return MTD_OK;
+    // one source, and the whole batch as one group of the finish
+    return metrics_launch(EachSources{{a, nullptr, nullptr}, {clip_a, 0, 0}}, 1, b, B, H, W, 1, out2, ws, (hipStream_t)stream);
 }
 
 extern "C" size_t mtd_image_metrics_each_ws_bytes(int na, int B, int H, int W) {
@@ -174,11 +147,5 @@ extern "C" int mtd_image_metrics_each(const float* const a[3], int na, const flo
         src.clip[k] = k < na ? clip_a[k] : 0;
         if (k < na && !a[k]) return MTD_EINVAL;
     }
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((W + MT - 1) / MT, (H + MT - 1) / MT, na * B);
-    hipLaunchKernelGGL(image_metrics_each_kernel, grid, dim3(256), 0, s, src, b, B, H, W, (double*)ws);
-    MTD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(image_metrics_each_finish_kernel, dim3(na * B), dim3(256), 0, s, (const double*)ws, metric_blocks(1, H, W), (double*)out);
-    MTD_LAUNCH_CHECK();
-    return MTD_OK;
+    return metrics_launch(src, na, b, B, H, W, na * B, out, ws, (hipStream_t)stream);
 }
