@@ -521,6 +521,33 @@ size_t mtd_image_metrics_each_ws_bytes(int na, int B, int H, int W);
 int mtd_image_metrics_each(const float* const a[3], int na, const float* b, int B, int H, int W, const int clip_a[3], double* out,
                            void* ws, void* stream);
 
+/* ---- further full-reference metrics of the test loop (module/piq: ssim.py multi_scale_ssim, vif.py vif_p, gmsd.py gmsd) --
+ * DESIGN 3.14.  Single-channel fp32 images (B, H, W) in [0, 1] (data_range 1), na in 1..3 sources a[k] against one target b, image
+ * by image.  which_mask: MTD_IQA_MS_SSIM | MTD_IQA_VIF | MTD_IQA_GMSD.
+ *   MS-SSIM  11 x 11 Gaussian (sigma 1.5) on valid windows, five levels weighted (0.0448, 0.2856, 0.3001, 0.2363, 0.1333),
+ *            C1 = 0.01^2, C2 = 0.03^2; between levels replicate-pad left and top by max(h % 2, w % 2), then a 2 x 2 average
+ *            pool; score = prod relu(v_l)^w_l, v_l the mean of the cs map (last level: of the SSIM map).  H, W >= 161.
+ *   VIFp     scales 1..4 with Gaussians of 17, 9, 5, 3 taps (sigma = taps / 5) on valid windows, each scale after the first
+ *            filtered with its own window and subsampled by two; score = (sum num + 1e-8) / (sum den + 1e-8) with
+ *            num = sum log10(1 + g^2 s_t / (s_v + sigma_n_sq)), den = sum log10(1 + s_t / sigma_n_sq).  sigma_n_sq > 0 is
+ *            taken on the [0, 1] scale as given (the vendored vif_p does not rescale to [0, 255]).  H, W >= 41.
+ *   GMSD     zero-pad bottom and right by max(H % 2, W % 2), 2 x 2 average pool, Prewitt / 3 with zero padding, GMS with
+ *            t = 170 / 255^2; score = population standard deviation of the GMS map.  H, W >= 2.
+ * out: (n selected metrics in the order above, na, B) doubles, the finished scores.  parts (optional, may be null):
+ * (na, B, MTD_IQA_PARTS) doubles, [0..9] MS-SSIM (cs mean, SSIM mean) of levels 0..4, [10..17] VIFp (num, den) of scales 1..4,
+ * [18..19] GMSD (mean, variance) of the GMS map; only the selected metrics' entries are written.  fp32 filter arithmetic, per-image
+ * sums in double in a fixed order: an image's numbers depend neither on the batch nor on its source slot.  a is read on the
+ * host during the call (its first na entries).  Null pointers, which_mask outside 1..7, na outside 1..3, a side below a
+ * selected metric's minimum, (na + 1) * B > 65535, H * W > 2^30, sigma_n_sq <= 0: MTD_EINVAL before any launch (the _ws_bytes
+ * query then returns 0). */
+#define MTD_IQA_MS_SSIM 1
+#define MTD_IQA_VIF 2
+#define MTD_IQA_GMSD 4
+#define MTD_IQA_PARTS 20
+size_t mtd_iqa_ws_bytes(int which_mask, int na, int B, int H, int W);
+int mtd_iqa_each(const float* const a[3], int na, const float* b, int B, int H, int W, int which_mask, float sigma_n_sq, double* out,
+                 double* parts, void* ws, void* stream);
+
 /* ---- perceptual metrics of the test loop (metrics.py:43-168: PL and TML on VGG-19 features; engine.py:139-140) ------
  * The convolutions of the feature stack are mtd_conv_* launches; these are the other pieces.  Maps are contiguous NHWC fp32,
  * 16-byte aligned (MTD_EALIGN).

@@ -276,6 +276,8 @@ def lib():
     sig("mtd_image_metrics_each_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_image_metrics_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, C.POINTER(ci), vp, vp, vp)
     sig("mtd_patch_gram_l1_each", ci, vp, vp, ci, ci, ci, ci, vp, ll, vp, vp)
+    sig("mtd_iqa_ws_bytes", sz, ci, ci, ci, ci, ci)
+    sig("mtd_iqa_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp)
     sig("mtd_maxpool2x2", ci, vp, vp, ci, ci, ci, ci, vp)
     sig("mtd_patch_gram_l1_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_patch_gram_l1", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
@@ -368,6 +370,7 @@ EXPORTS = [
     "mtd_image_metrics_each_ws_bytes", "mtd_image_metrics_each", "mtd_patch_gram_l1_each",
     "mtd_gray_png_rows_ws_bytes", "mtd_gray_png_rows",
     "mtd_stored_to_hu", "mtd_stored_to_window", "mtd_window_to_stored",
+    "mtd_iqa_ws_bytes", "mtd_iqa_each",
 ]
 
 

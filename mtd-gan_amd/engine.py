@@ -226,7 +226,32 @@ def _l1_each(loss, pred, target):
     return torch.stack([torch.as_tensor(loss(pred[i:i + 1], target[i:i + 1]), device=pred.device).reshape(()) for i in range(B)])
 
 
-def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows):
+_IQA_COLUMNS = {"ms_ssim": "MS_SSIM", "vif": "VIF", "gmsd": "GMSD"}
+
+
+def _iqa_option(model):
+    """`model.test_iqa` of test_MTD_GAN_Ours: absent or falsy -> None; True -> all of metrics.IQA_METRICS; a tuple of names from
+    it -> those, in the order of metrics.IQA_METRICS whatever the tuple's.  Anything else: ValueError, before anything runs on the device."""
+    cfg = getattr(model, "test_iqa", None)
+    names = ("ms_ssim", "vif", "gmsd")
+    if not cfg:
+        return None
+    if cfg is True:
+        return names
+    if not isinstance(cfg, (tuple, list)) or any(n not in names for n in cfg) or len(set(cfg)) != len(cfg):
+        raise ValueError(f"model.test_iqa: True or a tuple of names from {names}; got {cfg!r}")
+    return tuple(n for n in names if n in cfg)
+
+
+def _iqa_update(iqa, triples, meters):
+    """The meters of one sample (after the sample's other keys); returns its CSV cells, the pred values."""
+    for name, triple in zip(iqa, triples):
+        for who, v in zip(("input", "gt", "pred"), triple):
+            meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+    return tuple(t[2] for t in triples)
+
+
+def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa=None):
     """One loader batch of test_MTD_GAN_Ours under `model.test_per_slice`: B meter updates and B rows from one host read."""
     from . import kernels as K, metrics as M
     B, _, H, W = x.shape
@@ -237,11 +262,14 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
     if fid_features is not None:
         for rows_, f in zip(feats, M.compute_feat(x, y, clipped, extractor=fid_features)):
             rows_.append(f.float())
+    if iqa is not None:
+        parts.append(M.iqa_metrics_each(x, y, clipped, iqa).flatten())          # (metric, who, slice) float64, behind the others
     vals = torch.cat(parts).tolist()                  # every per-slice value of the batch in one device -> host copy
     l1 = vals[:B]
     sums = [[vals[B + (k * B + i) * 2:B + (k * B + i) * 2 + 2] for i in range(B)] for k in range(3)]
     six = [vals[7 * B + r * B:7 * B + (r + 1) * B] for r in range(6)] if vgg is not None else None
     pm = M._slice_triples(sums, H * W)
+    q0 = (13 if vgg is not None else 7) * B           # where the iqa block starts
     paths = batch_data.get("path_n_20") if isinstance(batch_data, dict) else None
     for i in range(B):
         meters.setdefault("L1_loss", _Meter()).update(l1[i], 1)
@@ -254,8 +282,9 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
         for name in ("rmse", "psnr", "ssim"):
             for who, v in zip(("input", "gt", "pred"), pm[name][i]):
                 meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+        more = _iqa_update(iqa, [tuple(vals[q0 + (r * 3 + k) * B + i] for k in range(3)) for r in range(len(iqa))], meters) if iqa is not None else ()
         path = paths[i] if paths is not None else f"slice_{len(rows)}"
-        rows.append((path,) + perceptual + (pm["rmse"][i][2], pm["psnr"][i][2], pm["ssim"][i][2]))
+        rows.append((path,) + perceptual + (pm["rmse"][i][2], pm["psnr"][i][2], pm["ssim"][i][2]) + more)
 
 
 class _PngSink:
@@ -429,7 +458,16 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     prediction back in stored pixel values (dicom_io.window_to_stored of the raw prediction: clipped, the reference's truncation,
     the input's own word where the input's HU lies outside the window): one launch and one device -> host copy per loader batch,
     read after the batch's metrics.  It needs `test_from_stored`, and like the PNGs `test_per_slice` for batches of more than one
-    slice (ValueError otherwise).  Without the attributes (or with falsy values) nothing changes."""
+    slice (ValueError otherwise).  Without the attributes (or with falsy values) nothing changes.
+    `model.test_iqa = True` (or a tuple of names from ("ms_ssim", "vif", "gmsd")) adds the reference's vendored piq
+    metrics MS-SSIM, VIFp and GMSD of (input, gt, clipped prediction) against gt on the HIP kernels of csrc/iqa.hip
+    (metrics.iqa_metrics_each): the result gains {input,gt,pred}_{ms_ssim,vif,gmsd} after the other per-sample keys and the CSV the
+    columns MS_SSIM, VIF, GMSD (of those chosen, in that order) after SSIM, holding the prediction's values.  On the default path a
+    batch gives one value per metric and image set (the mean over its slices, piq's reduction='mean'); under `test_per_slice` the
+    B values per slice travel in the batch's one device -> host copy.  Slices of at least 161 x 161 for MS-SSIM, 41 x 41 for
+    VIFp (ValueError otherwise).  Any other value of the attribute is refused (ValueError) before anything runs; without it (or
+    with a falsy value) nothing changes."""
+    _iqa_option(model)                                   # (a bad value is refused before anything else is set up)
     stored = _StoredInput.from_model(model)
     dcm = _DcmSink.from_model(model, stored)
     png = _PngSink.from_model(model, save_dir)
@@ -449,6 +487,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
     vgg = getattr(model, "perceptual_vgg", None)
     fid_features = getattr(model, "fid_features", None)
     per_slice = bool(getattr(model, "test_per_slice", False))
+    iqa = _iqa_option(model)
     feats = ([], [], [])
     meters = {}
     rows = []
@@ -472,7 +511,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         if dcm is not None:
             slices = dcm.begin(pred, words, table)             # likewise
         if per_slice:
-            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows)
+            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa)
             if png is not None:
                 png.submit(images, batch_data, k0)
             if dcm is not None:
@@ -495,8 +534,11 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         for name, triple in pm.items():
             for who, v in zip(("input", "gt", "pred"), triple):
                 meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+        more = ()
+        if iqa is not None:          # the batch is one sample: the mean over its slices, piq's reduction='mean' (one more host read)
+            more = _iqa_update(iqa, M.iqa_metrics_each(x, y, clipped, iqa).mean(dim=2).tolist(), meters)
         path = batch_data.get("path_n_20", [f"slice_{len(rows)}"])[0] if isinstance(batch_data, dict) else f"slice_{len(rows)}"
-        rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]))
+        rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]) + more)
         if png is not None:
             png.submit(images, batch_data, k0)
         if dcm is not None:
@@ -505,7 +547,8 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         import os
         os.makedirs(save_dir, exist_ok=True)
         with open(os.path.join(save_dir, "pred_results.csv"), "w") as f:
-            f.write(",PATH,PL,TML,RMSE,PSNR,SSIM\n" if vgg is not None else ",PATH,RMSE,PSNR,SSIM\n")
+            f.write((",PATH,PL,TML,RMSE,PSNR,SSIM" if vgg is not None else ",PATH,RMSE,PSNR,SSIM")
+                    + "".join("," + _IQA_COLUMNS[n] for n in iqa or ()) + "\n")
             for i, r in enumerate(rows):
                 f.write(f"{i}," + ",".join(str(v) for v in r) + "\n")
     if fid_features is not None:

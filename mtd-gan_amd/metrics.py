@@ -18,7 +18,11 @@ caller built -- as `extractor`.
 
 Per-slice forms for a batch of B slices taken as B samples (engine.test_MTD_GAN_Ours under `model.test_per_slice`):
 pixel_metrics_each / pixel_metrics_per_slice (`mtd_image_metrics_each`), patch_gram_l1_each (`mtd_patch_gram_l1_each`) and
-perceptual_metrics_per_slice.  Their reductions have the bits of the one-slice calls above."""
+perceptual_metrics_per_slice.  Their reductions have the bits of the one-slice calls above.
+
+Further full-reference metrics the reference vendors in module/piq -- MS-SSIM (ssim.py: multi_scale_ssim), VIFp (vif.py: vif_p)
+and GMSD (gmsd.py: gmsd) -- image by image on the HIP kernels of csrc/iqa.hip (`mtd_iqa_each`): iqa_metrics_each /
+iqa_metrics_per_slice and compute_MS_SSIM / compute_VIF / compute_GMSD (engine.test_MTD_GAN_Ours under `model.test_iqa`)."""
 import numpy as np
 import torch
 
@@ -126,6 +130,91 @@ def pixel_metrics_per_slice(input, target, pred):
     pixel_metrics(input[i:i+1], target[i:i+1], pred[i:i+1]).  Two launches and one device -> host copy for the batch."""
     sums = pixel_metrics_each(input, target, pred).tolist()
     return _slice_triples(sums, target.shape[2] * target.shape[3])
+
+
+# ================================================================================================ MS-SSIM, VIFp, GMSD
+IQA_METRICS = ("ms_ssim", "vif", "gmsd")                       # the order of the rows of iqa_metrics_each and of mtd_iqa_each's mask bits
+IQA_MIN_SIDE = {"ms_ssim": 161, "vif": 41, "gmsd": 2}          # piq's own limits (ssim.py:424, vif.py:58; gmsd pools 2 x 2)
+IQA_PARTS = 20
+
+
+def _iqa_which(which):
+    """The chosen metrics in the order of IQA_METRICS; ValueError for anything but a non-empty selection of those names."""
+    names = (which,) if isinstance(which, str) else tuple(which) if isinstance(which, (tuple, list)) else None
+    if not names or any(n not in IQA_METRICS for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"iqa metrics: a non-empty tuple of names from {IQA_METRICS} expected, got {which!r}")
+    return tuple(n for n in IQA_METRICS if n in names)
+
+
+def iqa_metrics_each(input, target, pred, which=IQA_METRICS, sigma_n_sq=2.0, parts=False):
+    """MS-SSIM, VIFp and GMSD (piq's multi_scale_ssim, vif_p and gmsd with their defaults, data_range 1) of every slice of
+    (input, target, pred) against the same slice of target, without a host read: a (len(which), 3, B) float64 device tensor, rows
+    in the order ms_ssim, vif, gmsd whatever the order of `which`.  With parts=True also the (3, B, 20) float64 stage values:
+    [0..9] MS-SSIM (cs mean, SSIM mean) of the five levels, [10..17] VIFp (num, den) of the four scales, [18..19] GMSD (mean,
+    variance) of the GMS map; zero for metrics not in `which`.  A slice's values depend neither on the batch it is in nor on
+    the other two image sets (mtd_iqa_each: fp32 filters, per-image sums in double in a fixed order).
+    `sigma_n_sq` is VIFp's visual-noise variance on the [0, 1] scale: the vendored vif_p does NOT rescale the images to
+    [0, 255], so its default 2.0 is taken as it stands; pass 2 / 255**2 for the convention of the original [0, 255] code.
+    MS-SSIM needs sides of at least 161, VIFp of at least 41, GMSD of at least 2 (ValueError, as piq raises)."""
+    which = _iqa_which(which)
+    for t in (input, target, pred):
+        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
+            raise AssertionError("iqa metrics expect (B,1,H,W) tensors of the same shape")
+        if not t.is_cuda:
+            raise RuntimeError("iqa metrics: HIP path needs CUDA tensors (no CPU fallback)")
+    B, _, H, W = target.shape
+    for n in which:
+        if H < IQA_MIN_SIDE[n] or W < IQA_MIN_SIDE[n]:
+            raise ValueError(f"iqa metrics: {n} needs images of at least {IQA_MIN_SIDE[n]}x{IQA_MIN_SIDE[n]}, got {H}x{W}")
+    if not sigma_n_sq > 0:
+        raise ValueError(f"iqa metrics: sigma_n_sq must be positive, got {sigma_n_sq!r}")
+    import ctypes
+    srcs = [t.contiguous().float() for t in (input, target, pred)]
+    mask = sum(1 << IQA_METRICS.index(n) for n in which)
+    L = _lib.lib()
+    dev = srcs[1].device
+    out = torch.empty((len(which), 3, B), dtype=torch.float64, device=dev)
+    stage = torch.zeros((3, B, IQA_PARTS), dtype=torch.float64, device=dev) if parts else None
+    ws = K.workspace(L.mtd_iqa_ws_bytes(mask, 3, B, H, W), dev)
+    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    _lib.check(L.mtd_iqa_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, mask, float(sigma_n_sq), out.data_ptr(),
+                              stage.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_iqa_each")
+    return (out, stage) if parts else out
+
+
+def _iqa_triples(which, vals):
+    """vals: iqa_metrics_each's tensor as nested lists -> dict metric -> list of B (input, gt, pred) triples."""
+    return {n: [tuple(vals[r][k][i] for k in range(3)) for i in range(len(vals[r][0]))] for r, n in enumerate(which)}
+
+
+def iqa_metrics_per_slice(input, target, pred, which=IQA_METRICS, sigma_n_sq=2.0):
+    """iqa_metrics_each as host numbers: dict metric -> list of B (input, gt, pred) triples (the kernels' float64
+    scores).  One device -> host copy for the batch."""
+    which = _iqa_which(which)
+    return _iqa_triples(which, iqa_metrics_each(input, target, pred, which, sigma_n_sq).tolist())
+
+
+def _iqa_mean(name, input, target, pred, data_range, **kw):
+    if data_range != 1.0:
+        raise NotImplementedError(f"{name}: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
+    return tuple(iqa_metrics_each(input, target, pred, (name,), **kw)[0].mean(dim=1).tolist())
+
+
+def compute_MS_SSIM(input, target, pred, data_range=1.0):
+    """piq's multi_scale_ssim(a, target) with its defaults for a = input, target, pred: (input, gt, pred) floats, each the mean
+    over the batch of the per-image scores (reduction='mean').  Sides of at least 161."""
+    return _iqa_mean("ms_ssim", input, target, pred, data_range)
+
+
+def compute_VIF(input, target, pred, data_range=1.0, sigma_n_sq=2.0):
+    """piq's vif_p(a, target) likewise.  The vendored vif_p does not rescale to [0, 255]: sigma_n_sq = 2.0 applies to the [0, 1]
+    images as they are (iqa_metrics_each).  Sides of at least 41."""
+    return _iqa_mean("vif", input, target, pred, data_range, sigma_n_sq=sigma_n_sq)
+
+
+def compute_GMSD(input, target, pred, data_range=1.0):
+    """piq's gmsd(a, target) likewise.  Sides of at least 2."""
+    return _iqa_mean("gmsd", input, target, pred, data_range)
 
 
 # ================================================================================================ perceptual metrics
