@@ -49,6 +49,9 @@ CONV_CASES = [
 
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv_fwd_dgrad_wgrad(hip_lib, case):
+    """Forward conv, data gradient and weight gradient of one layer through kernels.conv() / kernels.wgrad() against autograd.  conv()
+    sends the 3x3 cases of 64 to 512 channels to the Winograd kernels (the 32-channel, 4x4 and 1x1 cases reach the implicit GEMM);
+    per-kernel coverage of the implicit GEMM lives in tests/test_igemm_kernels_gpu.py."""
     from mtd_gan_amd import kernels as K
     B, Ci, Co, H, W, k, s, p = case
     x = rnd(B, Ci, H, W, seed=1).requires_grad_(True)
@@ -359,7 +362,10 @@ def plain_layer_fused(hip_lib, plan):
 @pytest.mark.parametrize("cfg", list(range(9)))
 def test_igemm_every_tile_config(hip_lib, cfg):
     """Each implicit-GEMM instantiation (forced through the tuning hook), with and without split-K, against F.conv2d:
-    forward 3x3 / 1x1 / strided 4x4-parity data gradient, on maps with borders inside every tile."""
+    forward 3x3 / 1x1 / strided 4x4-parity data gradient, on maps with borders inside every tile.  It goes through kernels.conv(),
+    which sends the first two 3x3 cases (64 and 128 input channels on even maps) to the Winograd kernels whatever the override, and an
+    override whose BN does not divide N (ids 4, 5, 8 on the N = 64 data gradient) is dropped; per-kernel coverage of the implicit GEMM,
+    with the kernel that ran asserted, lives in tests/test_igemm_kernels_gpu.py."""
     import ctypes as C
     from mtd_gan_amd import _lib, kernels as K
     L = _lib.lib()
