@@ -609,6 +609,36 @@ int mtd_fid_residual(const double* A, const double* Y, double scale, int D, doub
 int mtd_fid_distance(const double* mu1, const double* s1, const double* mu2, const double* s2, int D, double offset,
                      int max_iters, double* out, int* iters, void* ws, void* stream);
 
+/* ---- Kernel Inception Distance (module/piq/kid.py) from the same (N, D) fp32 feature rows -- DESIGN 3.15 ------------------
+ * For every subset s of S: the m rows X[xi[s][i]] and Y[yi[s][i]] (xi, yi: (S, m) int tables on the device), the polynomial
+ * kernel K(A, B) = (gamma A B^T + coef0)^degree (integer degree 1..8, by repeated multiplication) in float64 on
+ * v_mfma_f64_16x16x4_f64, and kid.py's _mmd2_and_variance on K_XX, K_XY, K_YY.  The m x m matrices are never stored: each
+ * 64 x 64 tile is reduced to its row sums, column sums, sum of squares and diagonal sums where it is computed.  No size is
+ * special, no buffer is padded, no floating-point atomics: two calls give the same bits, and a subset's values depend neither
+ * on its place among the S subsets nor on S.  The values of the index tables are the caller's to check (an index outside its
+ * matrix reads as a row of zeros).  Nothing is allocated or synchronised; all work is enqueued on `stream`.
+ *   mtd_kid_ws_bytes   bytes of `ws` (exactly S * 3 * ceil(m / 64)^2 tile records of MTD_KID_TILE_REC doubles); 0 = m or S out
+ *                      of range.
+ *   mtd_kid            out[0], out[1] = the means over the subsets, in subset order, of out[2 + 2 s] = mmd2 and out[3 + 2 s] =
+ *                      var_est of subset s (0.0 when want_var == 0); out holds 2 + 2 S doubles.  mmd_est: MTD_KID_UNBIASED
+ *                      (kid.py's default), MTD_KID_BIASED, MTD_KID_USTAT.  var_at_m: the m of kid.py:137 (the caller passes
+ *                      min(Nx, Ny) for kid.py's behaviour).  parts: NULL, or (S, MTD_KID_PARTS) doubles per subset:
+ *                        [0] Kt_XX_sum  [1] Kt_YY_sum  [2] K_XY_sum  [3] sum_diag_X  [4] sum_diag_Y  [5] trace(K_XY)
+ *                        [6] sum_diag2_X  [7] sum_diag2_Y  [8] Kt_XX_2_sum  [9] Kt_YY_2_sum  [10] K_XY_2_sum
+ *                        [11] |Kt_XX_sums|^2  [12] |Kt_YY_sums|^2  [13] |K_XY_sums_1|^2  [14] |K_XY_sums_0|^2
+ *                        [15] dot_XX_XY  [16] dot_YY_YX  [17] zeta1_est  [18] zeta2_est  [19] mmd2  [20] var_est
+ *                      ([17], [18], [20] are 0.0 when want_var == 0).
+ *                      MTD_EINVAL, nothing launched: a null X, Y, xi, yi, out or ws; m < 2; want_var with m < 3 or
+ *                      var_at_m < 2; D < 1; degree outside 1..8; S < 1; 3 S > 65535; m > Nx or m > Ny; m > 2^20; an unknown
+ *                      mmd_est. */
+#define MTD_KID_PARTS 21
+#define MTD_KID_TILE_REC 132
+enum { MTD_KID_UNBIASED = 0, MTD_KID_BIASED = 1, MTD_KID_USTAT = 2 };
+size_t mtd_kid_ws_bytes(int m, int S);
+int mtd_kid(const float* X, int Nx, const float* Y, int Ny, int D, const int* xi, const int* yi, int m, int S, int degree,
+            double gamma, double coef0, int mmd_est, int want_var, int var_at_m, double* out, double* parts, void* ws,
+            void* stream);
+
 /* ---- FID's InceptionV3 feature network (module/piq/feature_extractors/fid_inception.py:134-168 and the block forwards
  * :198-316, built by metrics.py:17-31 compute_feat) -- DESIGN 3.9 --------------------------------------------------------
  * The 94 convolutions are mtd_conv_* launches; these are the other pieces.  Maps are NHWC fp32 on the caller's stream; source and

@@ -288,6 +288,8 @@ def lib():
     sig("mtd_fid_gemm", ci, vp, vp, vp, ci, cd, cd, vp)
     sig("mtd_fid_residual", ci, vp, vp, cd, ci, vp, vp, vp)
     sig("mtd_fid_distance", ci, vp, vp, vp, vp, ci, cd, ci, vp, vp, vp, vp)
+    sig("mtd_kid_ws_bytes", sz, ci, ci)
+    sig("mtd_kid", ci, vp, ci, vp, ci, ci, vp, vp, ci, ci, ci, cd, cd, ci, ci, ci, vp, vp, vp, vp)
     sig("mtd_resize_bilinear", ci, vp, ll, ll, ll, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp)
     sig("mtd_pool3x3", ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp)
     sig("mtd_global_avgpool", ci, vp, ci, vp, ci, ci, ci, ci, ci, vp)
@@ -366,6 +368,7 @@ EXPORTS = [
     "mtd_sw_gather", "mtd_sw_blend", "mtd_sw_finish", "mtd_sw_blend_multi", "mtd_sw_finish_multi", "mtd_sw_gather_flags",
     "mtd_maxpool2x2", "mtd_patch_gram_l1_ws_bytes", "mtd_patch_gram_l1", "mtd_scaled_sums_f64",
     "mtd_fid_ws_bytes", "mtd_fid_stats", "mtd_fid_gemm", "mtd_fid_residual", "mtd_fid_distance",
+    "mtd_kid_ws_bytes", "mtd_kid",
     "mtd_resize_bilinear", "mtd_pool3x3", "mtd_global_avgpool",
     "mtd_image_metrics_each_ws_bytes", "mtd_image_metrics_each", "mtd_patch_gram_l1_each",
     "mtd_gray_png_rows_ws_bytes", "mtd_gray_png_rows",

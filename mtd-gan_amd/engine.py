@@ -243,6 +243,20 @@ def _iqa_option(model):
     return tuple(n for n in names if n in cfg)
 
 
+def _kid_option(model):
+    """`model.test_kid` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.kid_distance64's defaults); a dict ->
+    its keyword arguments (not `parts`).  It needs `model.fid_features`, whose feature rows it is computed from.  Anything
+    else: ValueError, before anything runs on the device."""
+    cfg = getattr(model, "test_kid", None)
+    if not cfg:
+        return None
+    if cfg is not True and not (isinstance(cfg, dict) and all(isinstance(k, str) for k in cfg) and "parts" not in cfg):
+        raise ValueError(f"model.test_kid: True or a dict of metrics.kid_distance64's keyword arguments (without `parts`); got {cfg!r}")
+    if getattr(model, "fid_features", None) is None:
+        raise ValueError("model.test_kid needs model.fid_features: KID is computed from the feature rows of that extractor")
+    return {} if cfg is True else dict(cfg)
+
+
 def _iqa_update(iqa, triples, meters):
     """The meters of one sample (after the sample's other keys); returns its CSV cells, the pred values."""
     for name, triple in zip(iqa, triples):
@@ -466,8 +480,16 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     batch gives one value per metric and image set (the mean over its slices, piq's reduction='mean'); under `test_per_slice` the
     B values per slice travel in the batch's one device -> host copy.  Slices of at least 161 x 161 for MS-SSIM, 41 x 41 for
     VIFp (ValueError otherwise).  Any other value of the attribute is refused (ValueError) before anything runs; without it (or
-    with a falsy value) nothing changes."""
+    with a falsy value) nothing changes.
+    `model.test_kid = True` (or a dict of metrics.kid_distance64's keyword arguments) adds piq's Kernel Inception
+    Distance after the loop, from the same feature rows as FID and therefore only with `model.fid_features` (ValueError
+    otherwise, before anything runs): the result gains input_kid / gt_kid / pred_kid behind the FID keys (metrics.compute_KID:
+    float64 on the HIP kernels of csrc/kid.hip, returned as float32) and, with ret_var, input_kid_var / gt_kid_var / pred_kid_var;
+    the three or six values cross in one device -> host copy.  The subsets are drawn from torch's global CPU generator as piq
+    draws them, three calls' worth in the order input, gt, pred.  The CSV does not change.  Without the attribute (or with a
+    falsy value) nothing changes."""
     _iqa_option(model)                                   # (a bad value is refused before anything else is set up)
+    _kid_option(model)
     stored = _StoredInput.from_model(model)
     dcm = _DcmSink.from_model(model, stored)
     png = _PngSink.from_model(model, save_dir)
@@ -488,6 +510,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
     fid_features = getattr(model, "fid_features", None)
     per_slice = bool(getattr(model, "test_per_slice", False))
     iqa = _iqa_option(model)
+    kid = _kid_option(model)
     feats = ([], [], [])
     meters = {}
     rows = []
@@ -552,7 +575,15 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
             for i, r in enumerate(rows):
                 f.write(f"{i}," + ",".join(str(v) for v in r) + "\n")
     if fid_features is not None:
-        fid = torch.stack(M.compute_FID(*(torch.cat(f, dim=0) for f in feats))).tolist()       # the three values in one device -> host copy
+        sets = [torch.cat(f, dim=0) for f in feats]
+        fid = torch.stack(M.compute_FID(*sets)).tolist()       # the three values in one device -> host copy
         for who, v in zip(("input", "gt", "pred"), fid):
             meters.setdefault(f"{who}_fid", _Meter()).update(v, 1)
+        if kid is not None:
+            triple = M.compute_KID(*sets, **kid)
+            with_var = bool(kid.get("ret_var"))
+            vals = torch.stack([t[j] for j in range(2) for t in triple] if with_var else list(triple)).tolist()       # three or six values, one copy
+            for j, name in enumerate(("kid", "kid_var") if with_var else ("kid",)):
+                for who, v in zip(("input", "gt", "pred"), vals[3 * j:3 * j + 3]):
+                    meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
     return {k: round(mm.global_avg, 7) for k, mm in meters.items()}

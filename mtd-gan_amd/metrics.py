@@ -22,7 +22,10 @@ perceptual_metrics_per_slice.  Their reductions have the bits of the one-slice c
 
 Further full-reference metrics the reference vendors in module/piq -- MS-SSIM (ssim.py: multi_scale_ssim), VIFp (vif.py: vif_p)
 and GMSD (gmsd.py: gmsd) -- image by image on the HIP kernels of csrc/iqa.hip (`mtd_iqa_each`): iqa_metrics_each /
-iqa_metrics_per_slice and compute_MS_SSIM / compute_VIF / compute_GMSD (engine.test_MTD_GAN_Ours under `model.test_iqa`)."""
+iqa_metrics_per_slice and compute_MS_SSIM / compute_VIF / compute_GMSD (engine.test_MTD_GAN_Ours under `model.test_iqa`).
+
+KID (module/piq/kid.py, vendored by the reference beside fid.py) from the same (N, D) feature rows as FID, in float64 on the HIP
+kernels of csrc/kid.hip (`mtd_kid`): kid_distance64 / compute_KID (engine.test_MTD_GAN_Ours under `model.test_kid`)."""
 import numpy as np
 import torch
 
@@ -551,6 +554,135 @@ def compute_FID(input_feats, target_feats, pred_feats):
     target's statistics are computed once and serve all three."""
     st = fid_statistics(target_feats)
     return tuple(fid_distance64(st if f is target_feats else fid_statistics(f), st).float() for f in (input_feats, target_feats, pred_feats))
+
+
+# ================================================================================================ KID
+KID_MMD_ESTS = ("unbiased", "biased", "u-statistic")          # MTD_KID_UNBIASED / _BIASED / _USTAT
+KID_PARTS = 21                                                # MTD_KID_PARTS; the names: include/mtdgan_hip.h
+KID_MAX_SUBSETS = 65535 // 3                                  # grid z of the tile kernel is 3 * S
+
+
+def _kid_feats(name, feats):
+    if not torch.is_tensor(feats) or feats.dim() != 2:
+        raise AssertionError(f"{name} expects (N, D) feature tensors")
+    if feats.shape[1] < 1:
+        raise ValueError(f"{name}: features of dimension 0")
+    if feats.dtype != torch.float32:
+        raise TypeError(f"{name}: fp32 features expected, got {feats.dtype}")
+    return feats.detach().contiguous()
+
+
+def kid_draw_subsets(n_pred, n_targ, m, n_subsets):
+    """The subsets as kid.py:230-232 draws them, from torch's global CPU generator: per subset first
+    torch.randperm(n_pred)[:m], then torch.randperm(n_targ)[:m] -- a caller's seeded generator stays in step with piq.  Two
+    (n_subsets, m) int64 CPU tensors.  Where a subset is the whole set, its indices are taken in sorted order (the draw is still
+    made): the result then does not depend on the seed, and differs from piq's, which sums the same terms in the drawn order,
+    only in rounding."""
+    pi, ti = [], []
+    for _ in range(n_subsets):
+        a = torch.randperm(n_pred)[:m]
+        b = torch.randperm(n_targ)[:m]
+        pi.append(torch.arange(n_pred) if m == n_pred else a)
+        ti.append(torch.arange(n_targ) if m == n_targ else b)
+    return torch.stack(pi), torch.stack(ti)
+
+
+def _kid_plan(n_pred, n_targ, D, degree, gamma, coef0, var_at_m, average, n_subsets, subset_size, ret_var, mmd_est, subsets):
+    """Every check of kid_distance64 that needs no device, and the draw: (pred_idx, trgt_idx) int32 CPU tables of shape (S, m) and
+    the scalar arguments of mtd_kid.  ValueError before the library is touched."""
+    import numbers
+    if isinstance(degree, bool) or not isinstance(degree, numbers.Integral) or not 1 <= degree <= 8:
+        raise ValueError(f"kid: degree must be an integer in 1..8, got {degree!r}")
+    if mmd_est not in KID_MMD_ESTS:
+        raise ValueError(f"kid: mmd_est must be one of {KID_MMD_ESTS}, got {mmd_est!r}")
+    if subsets is not None:
+        if not (isinstance(subsets, (tuple, list)) and len(subsets) == 2):
+            raise ValueError("kid: subsets must be a (pred_idx, trgt_idx) pair of (S, m) integer tensors")
+        pi, ti = (torch.as_tensor(t) for t in subsets)
+        if pi.dim() != 2 or pi.shape != ti.shape or pi.is_floating_point() or ti.is_floating_point() or pi.dtype == torch.bool or ti.dtype == torch.bool:
+            raise ValueError("kid: subsets must be a (pred_idx, trgt_idx) pair of (S, m) integer tensors of one shape")
+        if pi.is_cuda or ti.is_cuda:
+            raise ValueError("kid: subsets are checked on the host: pass CPU tensors (the call itself reads nothing back from the device)")
+        S, m = pi.shape
+    else:
+        S, m = (n_subsets, subset_size) if average else (1, n_pred)
+        if isinstance(S, bool) or isinstance(m, bool) or not isinstance(S, numbers.Integral) or not isinstance(m, numbers.Integral):
+            raise ValueError(f"kid: n_subsets and subset_size must be integers, got {S!r} and {m!r}")
+    if S < 1 or S > KID_MAX_SUBSETS:
+        raise ValueError(f"kid: 1 to {KID_MAX_SUBSETS} subsets expected, got {S}")
+    if m > n_pred or m > n_targ:
+        raise ValueError(f"kid: a subset of {m} rows cannot be drawn from sets of {n_pred} and {n_targ} rows (piq fails an assertion here)")
+    if m < 2:
+        raise ValueError(f"kid: subsets of at least two rows expected, got {m} (the estimate divides by m - 1)")
+    if ret_var and m < 3:
+        raise ValueError(f"kid: the variance estimate needs subsets of at least three rows, got {m} (it divides by m - 2)")
+    if var_at_m is None:
+        var_at_m = min(n_pred, n_targ)
+    if isinstance(var_at_m, bool) or not isinstance(var_at_m, numbers.Integral) or (ret_var and var_at_m < 2):
+        raise ValueError(f"kid: var_at_m must be an integer of at least 2, got {var_at_m!r}")
+    gamma = 1.0 / D if gamma is None else float(gamma)
+    if subsets is None:
+        pi, ti = kid_draw_subsets(n_pred, n_targ, m, S)
+    elif bool((pi < 0).any() or (pi >= n_pred).any() or (ti < 0).any() or (ti >= n_targ).any()):
+        raise ValueError("kid: a subset index lies outside its feature set")
+    return pi.to(torch.int32).contiguous(), ti.to(torch.int32).contiguous(), dict(
+        m=int(m), S=int(S), degree=int(degree), gamma=gamma, coef0=float(coef0), mmd_est=KID_MMD_ESTS.index(mmd_est),
+        want_var=1 if ret_var else 0, var_at_m=int(var_at_m))
+
+
+@torch.no_grad()
+def kid_distance64(pred_feats, target_feats, *, degree=3, gamma=None, coef0=1, var_at_m=None, average=False, n_subsets=50, subset_size=1000,
+                   ret_var=False, mmd_est="unbiased", subsets=None, parts=False):
+    """piq's KID (module/piq/kid.py) of two (N, D) fp32 CUDA feature sets in float64 on the HIP kernels of csrc/kid.hip (mtd_kid;
+    DESIGN 3.15): the MMD^2 estimate with the kernel (gamma <x, y> + coef0)^degree, gamma = 1 / D by default, averaged over the
+    subsets -- a 0-dim float64 device tensor, with ret_var the pair (score, variance estimate); with parts=True the (S,
+    KID_PARTS) float64 table of every named sum of each subset comes last.  No host read inside the call: the index tables go
+    host -> device, nothing comes back.
+
+    average=False: one subset of m = N_pred rows of each set; average=True: n_subsets subsets of subset_size rows.  The subsets
+    are drawn as piq draws them (kid_draw_subsets), from torch's global CPU generator, so torch.manual_seed(s) before the call
+    gives the subsets piq takes after the same seed; `subsets=(pred_idx, trgt_idx)`, two (S, m) integer CPU tensors, overrides
+    the draw (and average / n_subsets / subset_size).  Where a subset is the whole set its rows are taken in sorted order, so
+    the default call on equally long sets gives the same bits whatever the seed.  var_at_m defaults to min(N_pred, N_targ), as
+    piq's class computes it.  mmd_est: piq's "unbiased" (its class's only choice), "biased" or "u-statistic".
+
+    ValueError, before anything is launched: m > N_pred or m > N_targ (piq fails an assertion), m < 2, ret_var with m < 3 (piq
+    divides by zero in both), a degree that is not an integer in 1..8, an unknown mmd_est, an index outside its set.
+    KID(target, target) is not 0 under the unbiased estimator but a small negative number: piq's value, reproduced."""
+    x, y = _kid_feats("kid_distance64", pred_feats), _kid_feats("kid_distance64", target_feats)
+    if x.shape[1] != y.shape[1] or x.device != y.device:
+        raise AssertionError("kid_distance64 expects two feature sets of one dimension on one device")
+    pi, ti, a = _kid_plan(x.shape[0], y.shape[0], x.shape[1], degree, gamma, coef0, var_at_m, average, n_subsets, subset_size, ret_var, mmd_est, subsets)
+    if not (x.is_cuda and y.is_cuda):                  # (after the argument checks: those need no device)
+        raise RuntimeError("kid_distance64: HIP path needs CUDA tensors (no CPU fallback)")
+    L = _lib.lib()
+    dev = x.device
+    xi, yi = pi.to(dev, non_blocking=True), ti.to(dev, non_blocking=True)
+    out = torch.empty(2 + 2 * a["S"], dtype=torch.float64, device=dev)
+    table = torch.empty((a["S"], KID_PARTS), dtype=torch.float64, device=dev) if parts else None
+    ws = K.workspace(L.mtd_kid_ws_bytes(a["m"], a["S"]), dev)
+    _lib.check(L.mtd_kid(x.data_ptr(), x.shape[0], y.data_ptr(), y.shape[0], x.shape[1], xi.data_ptr(), yi.data_ptr(), a["m"], a["S"], a["degree"],
+                         a["gamma"], a["coef0"], a["mmd_est"], a["want_var"], a["var_at_m"], out.data_ptr(), table.data_ptr() if parts else None,
+                         ws.data_ptr(), K.stream_ptr()), "mtd_kid")
+    res = (out[0], out[1]) if ret_var else (out[0],)
+    if parts:
+        res = res + (table,)
+    return res if len(res) > 1 else res[0]
+
+
+@torch.no_grad()
+def compute_KID(input_feats, target_feats, pred_feats, **kw):
+    """(KID(input, target), KID(target, target), KID(pred, target)) as 0-dim float32 device tensors, the mirror of compute_FID;
+    with ret_var=True three (score, variance) pairs.  **kw: the keyword arguments of kid_distance64 (not `parts`).  Each of the
+    three is a call of its own and draws anew, in the order input, gt, pred -- what three piq calls after one seed give; the
+    target's subset is NOT shared between them."""
+    if kw.get("parts"):
+        raise ValueError("compute_KID: `parts` belongs to kid_distance64")
+    out = []
+    for f in (input_feats, target_feats, pred_feats):
+        r = kid_distance64(f, target_feats, **kw)
+        out.append(tuple(v.float() for v in r) if isinstance(r, tuple) else r.float())
+    return tuple(out)
 
 
 @torch.no_grad()
