@@ -479,6 +479,20 @@ int mtd_adamw_multi_pre(const mtd_adamw_tensor* tensors_dev, const mtd_adamw_ten
                         float beta2, float eps, float decay, float step_size, float inv_sqrt_bc2, void* stream);
 int mtd_adamw_multi_dyn(const mtd_adamw_tensor* tensors_dev, const mtd_adamw_tensor* tensors_host, int count,
                         float beta1, float beta2, float eps, const float* dyn, void* stream);
+/* The same update, and in the same launch the derived views of the 3x3 weights it has just written: what mtd_winograd_weights
+ * (wino[], px 4 / 6, not the split form) and mtd_pack_weights (pack[], T = 9) would write after it, bit for bit, without reading
+ * the weights back from memory.  spans[i] belongs to tensors[i]: N = 0 -- no views, the plain update; otherwise tensors[i] is a
+ * contiguous [N][C][9] weight with N % 16 == 0 and C % 16 == 0 and wino[wino_first .. wino_first + wino_count) /
+ * pack[pack_first .. pack_first + pack_count) are views of it -- src = p, st = 1 and (sn, sc) = (9 C, 9), view shape (N, C): the
+ * forward view, or (9, 9 C), view shape (C, N): the data-gradient view.  dyn != NULL: (decay, step_size, inv_sqrt_bc2) are
+ * read from dyn[0..2] as in mtd_adamw_multi_dyn; NULL: the three arguments as in mtd_adamw_multi_pre. */
+typedef struct { int N, C, wino_first, wino_count, pack_first, pack_count; } mtd_adamw_views_span;
+int mtd_adamw_views(const mtd_adamw_tensor* tensors_dev, const mtd_adamw_tensor* tensors_host, int count,
+                    const mtd_adamw_views_span* spans_dev, const mtd_adamw_views_span* spans_host,
+                    const mtd_wino_weight_desc* wino_dev, const mtd_wino_weight_desc* wino_host, int n_wino,
+                    const mtd_pack_desc* pack_dev, const mtd_pack_desc* pack_host, int n_pack,
+                    float beta1, float beta2, float eps, float decay, float step_size, float inv_sqrt_bc2,
+                    const float* dyn, void* stream);
 
 /* ---- loss terms (losses.py:10-15,99-138; networks.py:1962-1977,1998-2002), batched by descriptor table --
  * kind 0: m*(a-t)^2 with t = b[i] or tconst, m = (mx[i]-my[i] != 0) or 1   (ls_gan / NDS_Loss / F.mse_loss)

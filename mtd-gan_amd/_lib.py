@@ -129,6 +129,11 @@ class AdamwTensor(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_longlong)]
 
 
+class AdamwViewsSpan(C.Structure):
+    _fields_ = [("N", C.c_int), ("C", C.c_int), ("wino_first", C.c_int), ("wino_count", C.c_int), ("pack_first", C.c_int),
+                ("pack_count", C.c_int)]
+
+
 _lib = None
 
 
@@ -265,6 +270,7 @@ def lib():
     sig("mtd_adamw_multi", ci, vp, vp, ci, cf, cf, cf, cf, cf, ci, vp)
     sig("mtd_adamw_multi_dyn", ci, vp, vp, ci, cf, cf, cf, vp, vp)
     sig("mtd_adamw_multi_pre", ci, vp, vp, ci, cf, cf, cf, cf, cf, cf, vp)
+    sig("mtd_adamw_views", ci, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, ci, cf, cf, cf, cf, cf, cf, vp, vp)
     sig("mtd_loss_terms_ws_bytes", sz, ci)
     sig("mtd_loss_terms", ci, vp, ci, vp, vp, vp)
     sig("mtd_loss_term_grads", ci, vp, ci, vp)
@@ -350,7 +356,7 @@ EXPORTS = [
     "mtd_spec_mix_wgrad_reduce", "mtd_irfft_rows", "mtd_transpose64", "mtd_act_grad", "mtd_copy_channels",
     "mtd_upsample2x_fwd", "mtd_upsample2x_bwd", "mtd_pixel_shuffle2_fwd", "mtd_pixel_shuffle2_bwd", "mtd_mul", "mtd_pack_weights",
     "mtd_sn_ws_bytes", "mtd_sn_power_iter", "mtd_sn_power_iter_multi", "mtd_sn_grad_ws_bytes", "mtd_sn_grad", "mtd_pcgrad_ws_bytes",
-    "mtd_pcgrad_gram", "mtd_pcgrad_combine", "mtd_adamw_multi", "mtd_adamw_multi_dyn", "mtd_adamw_multi_pre", "mtd_loss_terms_ws_bytes", "mtd_loss_terms",
+    "mtd_pcgrad_gram", "mtd_pcgrad_combine", "mtd_adamw_multi", "mtd_adamw_multi_dyn", "mtd_adamw_multi_pre", "mtd_adamw_views", "mtd_loss_terms_ws_bytes", "mtd_loss_terms",
     "mtd_loss_term_grads", "mtd_clip01", "mtd_clip01_bwd", "mtd_edge_loss_ws_bytes", "mtd_edge_loss",
     "mtd_prof_enable", "mtd_prof_collect", "mtd_conv_igemm_override", "mtd_conv_wgrad_override", "mtd_upload", "mtd_image_metrics_ws_bytes", "mtd_image_metrics", "mtd_rfft_rows_any", "mtd_spec_mix_any", "mtd_irfft_rows_any",
     "mtd_spectral_gen_ws_bytes", "mtd_spectral_gen_plan", "mtd_rfft_rows_gen", "mtd_spec_mix_gen", "mtd_irfft_rows_gen",

@@ -40,6 +40,7 @@
 // of 4 (and at least wino_plan's threshold) take it; NB = 2 only (three positions x two n blocks = 96 accumulator registers).
 #define MTD_NO_API 1
 #include "conv_igemm.hip"
+#include "wino_weight_transform.h"
 
 #ifndef W_SPREAD
 // How the K step's load instructions are issued.  0 (rounds 3-4): in bursts -- PX patch loads + PW NB weight loads at the top of the
@@ -112,16 +113,8 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const WinoWDesc* __re
             for (int a = 0; a < 3; ++a)
 #pragma unroll
                 for (int b = 0; b < 3; ++b) g[a][b] = s[(long long)w.kmap[a * 3 + b] * w.st];
-            // t = G g  (4 x 3), u = t Gx^T (4 x PX);  G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1] down the rows,
-            // Gx = G (F(2,3)) or [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1] (F(4,3)) along them
             float t[4][3];
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                t[0][b] = g[0][b];
-                t[1][b] = 0.5f * (g[0][b] + g[1][b] + g[2][b]);
-                t[2][b] = 0.5f * (g[0][b] - g[1][b] + g[2][b]);
-                t[3][b] = g[2][b];
-            }
+            wino_w_rows(g, t);          // t = G g  (4 x 3); u = t Gx^T (4 x PX) below: wino_weight_transform.h
             if (split) {
                 // the transformed value, split exactly into three bf16 pieces (conv_winograd_split.h), plane p at
                 // ((xi (C/16) + ck) 3 + p) N 16 + n 16 + c16  (in bf16 elements)
@@ -150,27 +143,7 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const WinoWDesc* __re
                 }
                 continue;
             }
-            const long long xs = (long long)(w.C / 8) * w.N * 8;          // stride between positions xi = a * PX + b
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                float* o = w.dst + (((long long)(a * PXr) * (w.C / 8) + ck) * w.N + n) * 8 + c8;
-                const float t0 = t[a][0], t1 = t[a][1], t2 = t[a][2];
-                if (PXr == 6) {
-                    const float e = (t0 + t2) * (1.f / 6.f), f = t1 * (1.f / 6.f);           // (t0 + t2) / 6, t1 / 6
-                    const float h = t0 * (1.f / 24.f) + t2 * (1.f / 6.f), k = t1 * (1.f / 12.f);
-                    o[0] = 0.25f * t0;
-                    o[xs] = -e - f;
-                    o[2 * xs] = -e + f;
-                    o[3 * xs] = h + k;
-                    o[4 * xs] = h - k;
-                    o[5 * xs] = t2;
-                } else {
-                    o[0] = t0;
-                    o[xs] = 0.5f * (t0 + t1 + t2);
-                    o[2 * xs] = 0.5f * (t0 - t1 + t2);
-                    o[3 * xs] = t2;
-                }
-            }
+            wino_w_store(w.dst, w.N, w.C, PXr, t, n, ck, c8);
         }
     }
 }

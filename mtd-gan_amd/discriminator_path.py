@@ -11,6 +11,7 @@ weight_orig in place and scale their accumulators by 1/sigma; the weight gradien
 from . import _options
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -166,15 +167,20 @@ SN_ACT_DOT = _options.lab("MTD_SN_ACT_DOT", "1") != "0"        # the spectral-no
 SKIP_IN_CAT = _options.lab("MTD_SKIP_IN_CAT", "1") != "0"      # trunk outputs written into the pixel-level decoder's concatenated buffers
 
 
-def _sn_forward(P, train, device):
-    """Power iteration + sigma for all 45 layers (4 launches).  Returns (sig[45,2], u_save, v_save)."""
+def _sn_forward(P, train, device, only=None, out=None):
+    """Power iteration + sigma for all 45 layers (4 launches).  Returns (sig[45,2], u_save, v_save).
+    only: a predicate on the layer name -- the launches cover those layers alone; out: the three tensors of an earlier call,
+    filled in for these layers (the layers are independent: a pass in two ranges gives what one pass gives)."""
     L = _lib.lib()
-    sig = torch.empty((len(SN_SPECS), 2), dtype=torch.float32, device=device)
-    u_save = torch.empty(SN_ROWS_TOTAL, dtype=torch.float32, device=device)
-    v_save = torch.empty(SN_COLS_TOTAL, dtype=torch.float32, device=device)
+    if out is not None:
+        sig, u_save, v_save = out
+    else:
+        sig = torch.empty((len(SN_SPECS), 2), dtype=torch.float32, device=device)
+        u_save = torch.empty(SN_ROWS_TOTAL, dtype=torch.float32, device=device)
+        v_save = torch.empty(SN_COLS_TOTAL, dtype=torch.float32, device=device)
     structs = []
     for i, (n, rows, cols) in enumerate(SN_SPECS):
-        if n + ".weight_orig" not in P:                        # ablation subsets: no such layer, its sigma slot stays unused
+        if n + ".weight_orig" not in P or (only is not None and not only(n)):     # ablation subsets: no such layer, its sigma slot stays unused
             continue
         s = _lib.SnLayer()
         s.w = P[n + ".weight_orig"].data_ptr()
@@ -185,12 +191,39 @@ def _sn_forward(P, train, device):
         s.v_save = v_save.data_ptr() + 4 * SN_COL_OFF[i]
         s.rows, s.cols = rows, cols
         structs.append(s)
+    if not structs:
+        return sig, u_save, v_save
     dev_tab, host_arr = K.device_table(structs, device)
     need = L.mtd_sn_ws_bytes(C.cast(host_arr, C.c_void_p), len(structs))
     ws = K.workspace(need, device)
     K.check(L.mtd_sn_power_iter(dev_tab.data_ptr(), C.cast(host_arr, C.c_void_p), len(structs), 1 if train else 0, ws.data_ptr(),
                                 K.stream_ptr()), "mtd_sn_power_iter")
     return sig, u_save, v_save
+
+
+# ---- the D-to-G hand-over in two ranges (train_step.d_optimizer_step).  The optimizer launch of the "deep" layers -- everything
+# but trunk levels 1 .. TAIL_SPLIT_LEVELS -- is on the side stream; the next forward pass keeps that range's derived views and power
+# iteration there too and waits for the stream only where it first reads a deep layer: conv41.  Levels 1-3 hold a few per cent of
+# the weight bytes and most of the forward's matrix work, which so runs beside the memory-bound tail of the other 90 %.
+TAIL_SPLIT_LEVELS = 3
+_SHALLOW = re.compile(r"(?:conv[1-%d][12]|down[1-%d])\." % (TAIL_SPLIT_LEVELS, TAIL_SPLIT_LEVELS))
+_tail_pending = {}       # device index -> True while a deep range's optimizer launch waits on the side stream, unjoined
+
+
+def is_shallow(name):
+    """Does this parameter / layer name (state_dict style, with or without a suffix) belong to trunk levels 1-3?"""
+    return _SHALLOW.match(name + ".") is not None
+
+
+def tail_on_side(device):
+    """train_step.d_optimizer_step: the deep range's update is on the side stream from now on."""
+    _tail_pending[device.index if device.index is not None else torch.cuda.current_device()] = True
+
+
+def settle_tail(device):
+    """Whoever reads the discriminator's weights without going through disc_forward's split waits for the side stream here."""
+    if _tail_pending.pop(device.index if device.index is not None else torch.cuda.current_device(), False):
+        K.side_stream(device).join()
 
 
 SN_FUSED_ITERS = _options.lab("MTD_SN_FUSED_ITERS", "1") != "0"      # d_loss: its four power iterations share passes over the weights (round 6)
@@ -276,10 +309,29 @@ def disc_forward(P, x, train, drop_mask, need_rec, save, sn=None, sn2=None, pair
     B = x.shape[0]
     dev = x.device
     tp = Tape()
-    K.prepack(conv_views(P, save))
-    K.prepack_winograd(winograd_views(P, save))
-    K.prepack_winograd_s2(winograd_s2_views(P, save))
-    tp.sig, tp.u_save, tp.v_save = sn if sn is not None else _sn_forward(P, train, dev)
+    split = sn is None and _tail_pending.get(dev.index if dev.index is not None else torch.cuda.current_device(), False)
+    if not split:
+        settle_tail(dev)
+        K.prepack(conv_views(P, save))
+        K.prepack_winograd(winograd_views(P, save))
+        K.prepack_winograd_s2(winograd_s2_views(P, save))
+        tp.sig, tp.u_save, tp.v_save = sn if sn is not None else _sn_forward(P, train, dev)
+    else:
+        # levels 1-3 here; the rest behind its optimizer launch on the side stream, joined at conv41 below
+        shallow_w = {id(P[k]) for k in P if is_shallow(k)}
+        deep_sn = lambda n: not is_shallow(n)
+        cv, wv, sv = conv_views(P, save), winograd_views(P, save), winograd_s2_views(P, save)
+        K.prepack([v for v in cv if id(v[0]) in shallow_w])
+        K.prepack_winograd([v for v in wv if id(v[0]) in shallow_w])
+        K.prepack_winograd_s2([v for v in sv if id(v[0]) in shallow_w])
+        tp.sig, tp.u_save, tp.v_save = out = _sn_forward(P, train, dev, only=is_shallow)
+
+        def deep_range():
+            K.prepack([v for v in cv if id(v[0]) not in shallow_w])
+            K.prepack_winograd([v for v in wv if id(v[0]) not in shallow_w])
+            K.prepack_winograd_s2([v for v in sv if id(v[0]) not in shallow_w])
+            _sn_forward(P, train, dev, only=deep_sn, out=out)
+        K.side_stream(dev).run(deep_range, fork=False)          # (the stream holds this range's update; nothing of the main stream's is read)
     tp.pair = int(pair)
     if tp.pair:
         if sn is None or sn2 is None or not (0 < tp.pair < B):
@@ -293,6 +345,8 @@ def disc_forward(P, x, train, drop_mask, need_rec, save, sn=None, sn2=None, pair
     # pixel stride): one copy of the skip per level and pass instead of two (18 launches of 3-25 us per iteration less).
     seg_cat = {}
     for l, co in enumerate(CH, start=1):
+        if l == TAIL_SPLIT_LEVELS + 1:
+            settle_tail(dev)                 # the first conv that reads a deep layer
         g3 = K.geom_fwd(B, h, h, 3, 1, 1)
         a = K.empty_nhwc(B, h, h, co, x)
         _sn_conv(P, tp, f"conv{l}1", t, a, g3, co, cin, 3, ACT_LRELU)

@@ -25,7 +25,11 @@ def train_iteration(model, x, y, optimizer_G, optimizer_D, method_D, dp=None):
         d_losses.backward()                 # engine.py:56-63: the ablation wrappers return one scalar
         if dp is not None:
             dp.all_reduce_avg_list([p.grad for p in D.parameters() if p.grad is not None])
-    optimizer_D.step()
+    if d_losses.is_cuda:
+        from .train_step import d_optimizer_step
+        d_optimizer_step(D, optimizer_D, dp)         # FusedAdamW on one GPU: the update's launch writes the 3x3 weights' views too
+    else:
+        optimizer_D.step()
     # ---- Generator
     optimizer_G.zero_grad()
     G.zero_grad()
@@ -34,6 +38,9 @@ def train_iteration(model, x, y, optimizer_G, optimizer_D, method_D, dp=None):
     if dp is not None:
         _all_reduce_generator_grads(model, G, dp)
     optimizer_G.step()
+    if d_losses.is_cuda:
+        from . import discriminator_path
+        discriminator_path.settle_tail(d_losses.device)      # (joined by the G step's discriminator pass already, unless that pass never ran)
     names = ["d_loss"] + list(d_details.keys()) + ["g_loss"] + list(g_details.keys())
     if d_losses.is_cuda:
         from . import kernels as K

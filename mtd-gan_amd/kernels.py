@@ -1780,6 +1780,79 @@ def adamw_multi_pre(params, grads, exp_avg, exp_avg_sq, beta1, beta2, eps, scala
                                 float(scalars[0]), float(scalars[1]), float(scalars[2]), stream_ptr()), "mtd_adamw_multi_pre")
 
 
+def adamw_views(params, grads, exp_avg, exp_avg_sq, beta1, beta2, eps, wino_views, pack_views, scalars=None, dyn_ptr=None):
+    """The update of adamw_multi_pre (scalars) / adamw_multi_dyn (dyn_ptr) and, in the same launch, those of the derived views
+    -- wino_views as prepack_winograd takes them, pack_views as prepack does -- that belong to contiguous 3x3 weights [N][C][3][3]
+    among params with N and C multiples of 16 (mtd_adamw_views): the views leave from the values the update has in hand instead of
+    being read back from memory by the next prepack_winograd / prepack, which find them current in the cache and skip them.
+    Every other view is left to those two.  The caller has dropped the parameters' stale views already (weights_changed)."""
+    L = _lib.lib()
+    where, structs, spans = {}, [], []
+    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avg, exp_avg_sq)):
+        t = _lib.AdamwTensor()
+        t.p, t.g, t.m, t.v, t.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+        structs.append(t)
+        spans.append(([], []))
+        if p.dim() == 4 and tuple(p.shape[2:]) == (3, 3) and p.is_contiguous() and p.shape[0] % 16 == 0 and p.shape[1] % 16 == 0:
+            where[p.data_ptr()] = i
+
+    def of_tensor(w, N, Cc, w_sn, w_sc):
+        """index of the tensor this is the forward or the transposed view of, or None"""
+        i = where.get(w.data_ptr())
+        if i is None or w is not params[i]:
+            return None
+        n, c = w.shape[0], w.shape[1]
+        return i if (N, Cc, w_sn, w_sc) in ((n, c, 9 * c, 9), (c, n, 9, 9 * c)) else None
+
+    done = []
+    for v in wino_views:
+        w, N, Cc, w_sn, w_sc, geom = v[:6]
+        i = of_tensor(w, N, Cc, w_sn, w_sc)
+        if i is None or not winograd_takes(geom, N, Cc, v[6] if len(v) > 6 else {}):
+            continue
+        kmap, px = _wino_kmap(geom), winograd_patch_w(geom, N, Cc)
+        ident = (w.data_ptr(), N, Cc, w_sn, w_sc, "wino", kmap, px)
+        if px not in (4, 6) or max(kmap) > 8 or any(ident == d[0] for d in done):      # (the split-bf16 form stays with prepack_winograd)
+            continue
+        d, dst = _wino_desc(w, N, Cc, w_sn, w_sc, kmap, w.device, px)
+        spans[i][0].append(d)
+        done.append((ident, (w.data_ptr(), w._version, _pack_epoch) + ident[1:], dst, w))
+    for (w, N, Cc, w_sn, w_sc) in pack_views:
+        i = of_tensor(w, N, Cc, w_sn, w_sc)
+        if i is None or (Cc % 32) or (N % 32) or not (w_sc != 1 or w.data_ptr() % 16 or w_sn % 4):       # (prepack's own conditions)
+            continue
+        ident = (w.data_ptr(), N, Cc, w_sn, w_sc)
+        if any(ident == d[0] for d in done):
+            continue
+        dst = _view_buffer(ident, (9, N, Cc), w.device)
+        d = _lib.PackDesc()
+        d.src, d.dst, d.N, d.C, d.T, d.sn, d.sc = w.data_ptr(), dst.data_ptr(), N, Cc, 9, w_sn, w_sc
+        spans[i][1].append(d)
+        done.append((ident, (w.data_ptr(), w._version, _pack_epoch) + ident[1:], dst, w))
+    wino, pack, span_structs = [], [], []
+    for p, (ws, ps) in zip(params, spans):
+        s = _lib.AdamwViewsSpan()
+        if ws or ps:
+            s.N, s.C, s.wino_first, s.wino_count, s.pack_first, s.pack_count = p.shape[0], p.shape[1], len(wino), len(ws), len(pack), len(ps)
+        wino += ws
+        pack += ps
+        span_structs.append(s)
+    dev = params[0].device
+    tab, host = device_table(structs, dev)
+    stab, shost = device_table(span_structs, dev)
+    wtab, whost = device_table(wino, dev) if wino else (None, None)
+    ptab, phost = device_table(pack, dev) if pack else (None, None)
+    sc = scalars if scalars is not None else (0.0, 0.0, 0.0)
+    check(L.mtd_adamw_views(tab.data_ptr(), C.cast(host, C.c_void_p), len(structs), stab.data_ptr(), C.cast(shost, C.c_void_p),
+                            wtab.data_ptr() if wino else None, C.cast(whost, C.c_void_p) if wino else None, len(wino),
+                            ptab.data_ptr() if pack else None, C.cast(phost, C.c_void_p) if pack else None, len(pack),
+                            float(beta1), float(beta2), float(eps), float(sc[0]), float(sc[1]), float(sc[2]),
+                            C.c_void_p(dyn_ptr) if dyn_ptr is not None else None, stream_ptr()), "mtd_adamw_views")
+    for ident, key, dst, w in done:
+        _remember(_pack_cache, ident, key, (dst, w))
+    return len(wino), len(pack)
+
+
 def adamw_multi(params, grads, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, wd):
     L = _lib.lib()
     structs = []

@@ -65,8 +65,16 @@ class FusedAdamW(torch.optim.Optimizer):
                 slot.set_inplace(self._scalars(group, step))
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, views=None, split=None):
+        """views = (Winograd views, [tap][n][c] views) as kernels.prepack_winograd / kernels.prepack take them: those that belong
+        to 3x3 weights of this optimizer leave in the update's own launch (kernels.adamw_views), the parameters themselves bit
+        for bit what the plain launch writes.
+        split = (ids of parameters, kernels.SideStream): those parameters get a launch of their own on that stream, ordered
+        after everything enqueued so far; the caller joins the stream before anything reads them (train_step.d_optimizer_step).
+        The same update per element either way."""
         self._captured = []
+        if views is not None:       # (first: the fused launch enters its views in the cache as current)
+            K.weights_changed([p for group in self.param_groups for p in group["params"] if p.grad is not None])
         for gi, group in enumerate(self.param_groups):
             by_step = {}
             for p in group["params"]:
@@ -83,24 +91,42 @@ class FusedAdamW(torch.optim.Optimizer):
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 by_step.setdefault(st["step"], []).append((p, g, st["exp_avg"], st["exp_avg_sq"]))
             for step, items in by_step.items():
-                b1, b2 = group["betas"]
-                if not self.graph_mode:
-                    # eager launch: the step-dependent scalars travel as kernel arguments
-                    K.adamw_multi_pre([i[0] for i in items], [i[1] for i in items], [i[2] for i in items], [i[3] for i in items],
-                                      b1, b2, group["eps"], self._scalars(group, step))
+                if split is None:
+                    self._launch(gi, group, step, items, views)
                     continue
-                # hipGraph capture: kernel arguments are frozen, the scalars are read from a pinned slot instead
-                slot = self._dyn.get((gi, len(self._captured)))
-                if slot is None:
-                    slot = K.HostScalars(items[0][0].device, 3, torch.float32)
-                    self._dyn[(gi, len(self._captured))] = slot
-                slot.set(self._scalars(group, step))
-                self._captured.append((slot, gi, [it[0] for it in items]))
-                K.adamw_multi_dyn([i[0] for i in items], [i[1] for i in items], [i[2] for i in items], [i[3] for i in items],
-                                  b1, b2, group["eps"], slot.device_ptr())
-                slot.consumed()
-        # parameters were updated through raw pointers: their packed weight views (and only theirs) are stale
-        K.weights_changed([p for group in self.param_groups for p in group["params"] if p.grad is not None])
+                here = [it for it in items if id(it[0]) not in split[0]]
+                there = [it for it in items if id(it[0]) in split[0]]
+                if here:
+                    self._launch(gi, group, step, here, views)
+                if there:
+                    split[1].run(lambda: self._launch(gi, group, step, there, views))
+        if views is None:
+            # parameters were updated through raw pointers: their packed weight views (and only theirs) are stale
+            K.weights_changed([p for group in self.param_groups for p in group["params"] if p.grad is not None])
+
+    def _launch(self, gi, group, step, items, views):
+        """One launch over items = [(p, g, exp_avg, exp_avg_sq)] of one group and step count, on the current stream."""
+        b1, b2 = group["betas"]
+        cols = [[it[k] for it in items] for k in range(4)]
+        if not self.graph_mode:
+            # eager launch: the step-dependent scalars travel as kernel arguments
+            if views is not None:
+                K.adamw_views(*cols, b1, b2, group["eps"], views[0], views[1], scalars=self._scalars(group, step))
+            else:
+                K.adamw_multi_pre(*cols, b1, b2, group["eps"], self._scalars(group, step))
+            return
+        # hipGraph capture / recorded list: kernel arguments are frozen, the scalars are read from a pinned slot instead
+        slot = self._dyn.get((gi, len(self._captured)))
+        if slot is None:
+            slot = K.HostScalars(items[0][0].device, 3, torch.float32)
+            self._dyn[(gi, len(self._captured))] = slot
+        slot.set(self._scalars(group, step))
+        self._captured.append((slot, gi, cols[0]))
+        if views is not None:
+            K.adamw_views(*cols, b1, b2, group["eps"], views[0], views[1], dyn_ptr=slot.device_ptr())
+        else:
+            K.adamw_multi_dyn(*cols, b1, b2, group["eps"], slot.device_ptr())
+        slot.consumed()
 
 
 def get_optimizer(name, model, lr):

@@ -404,6 +404,7 @@ def d_loss(method, x, y):
     # (D(clip(real_rec)), D(clip(fake_rec))).  Each pass keeps its own spectral-norm state: the four power iterations run
     # first, in the reference's order, and every conv applies the 1/sigma of the half it is computing (scale2 /
     # scale_split).  Same arithmetic per image; half the launches, twice the pixels per launch on the deep 4x4 .. 1x1 layers.
+    DP.settle_tail(dev)                       # (a deep range still on the side stream: only if no G step followed the last D step)
     K.prepack(DP.conv_views(P, True))
     K.prepack_winograd(DP.winograd_views(P, True))
     K.prepack_winograd_s2(DP.winograd_s2_views(P, True))
@@ -427,6 +428,33 @@ def d_loss(method, x, y):
     details = {k: v[i] for i, k in enumerate(keys)}
     losses._mtd_tape = DStepTape(method, P, (t12, t34), ((re, rd, rr), (fe, fd, fr), (rre, rrd), (rfe, rfd), r12), xn, yn, fn)
     return losses, details
+
+
+# The D optimizer's launch also writes the derived views of the 3x3 weights it updates (kernels.adamw_views, mtd_adamw_views):
+# the G step's discriminator forward then finds them current instead of reading the 200 MB of 3x3 weights back for them.
+TAIL_FUSED = _options.lab("MTD_TAIL_FUSED", "1") != "0"
+# ... and the hand-over runs in two ranges: trunk levels 1-3 on the main stream, everything else -- 90 % of the bytes, needed last --
+# on the side stream under the G step's level 1-3 convs (discriminator_path.tail_on_side; disc_forward joins at conv41).
+# 1: in an iteration that is being recorded as a launch list (the replays keep the stream order); 2: in eager iterations too; 0: never
+TAIL_SPLIT = int(_options.lab("MTD_TAIL_SPLIT", "1"))
+
+
+def d_optimizer_step(D, optimizer_D, dp=None):
+    """optimizer_D.step() at the end of the D step (engine.train_iteration).  A FusedAdamW on a single GPU gets the views the
+    next discriminator pass will ask for and, where TAIL_SPLIT says so, the side stream for the deep range; the data-parallel
+    path and any other optimizer step as before."""
+    from .optimizers import FusedAdamW
+    if not (dp is None and isinstance(optimizer_D, FusedAdamW) and hasattr(D, "_param_dict") and (TAIL_FUSED or TAIL_SPLIT)
+            and any(p.is_cuda for p in D.parameters())):
+        return optimizer_D.step()
+    P = D._param_dict()
+    views = (DP.winograd_views(P, True), DP.conv_views(P, True)) if TAIL_FUSED else None
+    split = None
+    side = K.side_stream(next(iter(P.values())).device)
+    if side.enabled and not torch.cuda.is_current_stream_capturing() and (TAIL_SPLIT >= 2 or (TAIL_SPLIT == 1 and K.RECORDING is not None)):
+        split = ({id(w) for k, w in P.items() if not DP.is_shallow(k)}, side)
+        DP.tail_on_side(side.stream.device)
+    return optimizer_D.step(views=views, split=split)
 
 
 def _gkey(x, gparams):
