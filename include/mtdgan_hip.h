@@ -562,6 +562,27 @@ size_t mtd_iqa_ws_bytes(int which_mask, int na, int B, int H, int W);
 int mtd_iqa_each(const float* const a[3], int na, const float* b, int B, int H, int W, int which_mask, float sigma_n_sq, double* out,
                  double* parts, void* ws, void* stream);
 
+/* ---- Haar wavelet perceptual similarity index of the test loop (module/piq: haarpsi.py haarpsi, scales = 3) -- DESIGN 3.16.
+ * Single-channel fp32 images (B, H, W) in [0, 1] (data_range 1), na in 1..3 sources a[k] against one target b, image by image.
+ *   rescale by 255; with subsample != 0 zero-pad bottom and right by max(H % 2, W % 2) (the same pad in both dimensions) and
+ *   take a 2 x 2 average pool with stride 2 (floor); for k = 2, 4, 8 zero-pad k/2 - 1 on top and left and k/2 on bottom and right
+ *   and cross-correlate with the k x k Haar filter (top k/2 rows +1/k, bottom k/2 rows -1/k) and with its transpose; per
+ *   orientation w = max(|cx|, |cy|) at k = 8 and sim = the mean over k = 2, 4 of (2 |cx| |cy| + c) / (cx^2 + cy^2 + c);
+ *   num = sum sigmoid(alpha sim) w and den = sum w over both orientations and all pixels; s = (num + eps) / (den + eps) with
+ *   float32's eps; score = (log(s / (1 - s)) / alpha)^2 (two all-zero images: +inf, as piq gives).
+ * out: (na, B) doubles, the finished scores.  parts (optional, may be null): (na, B, MTD_HAARPSI_PARTS) doubles, (num, den) of
+ * the filter as it is and then of its transpose.  fp32 filter arithmetic; similarity, sigmoid and per-image sums in double in a
+ * fixed order: an image's numbers depend neither on the batch nor on its source slot.  c and alpha arrive as floats (piq's
+ * float32 call rounds them likewise).  a is read on the host during the call (its first na entries).  ws: mtd_haarpsi_ws_bytes.
+ * Null pointers, na outside 1..3, B < 1, na * B > 65535, a side below MTD_HAARPSI_MIN_SIDE (piq's 2^(scales + 1), with subsample
+ * or without), H * W > 2^30, more than 65535 tile rows, c <= 0, alpha <= 0: MTD_EINVAL before any launch (the _ws_bytes query
+ * then returns 0). */
+#define MTD_HAARPSI_PARTS 4
+#define MTD_HAARPSI_MIN_SIDE 16
+size_t mtd_haarpsi_ws_bytes(int na, int B, int H, int W, int subsample);
+int mtd_haarpsi_each(const float* const a[3], int na, const float* b, int B, int H, int W, int subsample, float c, float alpha,
+                     double* out, double* parts, void* ws, void* stream);
+
 /* ---- perceptual metrics of the test loop (metrics.py:43-168: PL and TML on VGG-19 features; engine.py:139-140) ------
  * The convolutions of the feature stack are mtd_conv_* launches; these are the other pieces.  Maps are contiguous NHWC fp32,
  * 16-byte aligned (MTD_EALIGN).

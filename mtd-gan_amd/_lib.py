@@ -284,6 +284,8 @@ def lib():
     sig("mtd_patch_gram_l1_each", ci, vp, vp, ci, ci, ci, ci, vp, ll, vp, vp)
     sig("mtd_iqa_ws_bytes", sz, ci, ci, ci, ci, ci)
     sig("mtd_iqa_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp)
+    sig("mtd_haarpsi_ws_bytes", sz, ci, ci, ci, ci, ci)
+    sig("mtd_haarpsi_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, cf, cf, vp, vp, vp, vp)
     sig("mtd_maxpool2x2", ci, vp, vp, ci, ci, ci, ci, vp)
     sig("mtd_patch_gram_l1_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_patch_gram_l1", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
@@ -380,6 +382,7 @@ EXPORTS = [
     "mtd_gray_png_rows_ws_bytes", "mtd_gray_png_rows",
     "mtd_stored_to_hu", "mtd_stored_to_window", "mtd_window_to_stored",
     "mtd_iqa_ws_bytes", "mtd_iqa_each",
+    "mtd_haarpsi_ws_bytes", "mtd_haarpsi_each",
 ]
 
 

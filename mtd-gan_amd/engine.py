@@ -264,6 +264,29 @@ def _kid_option(model):
     return {} if cfg is True else dict(cfg)
 
 
+def _haarpsi_option(model):
+    """`model.test_haarpsi` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.haarpsi_each's defaults); a
+    dict with keys from c, alpha (positive numbers) and subsample (a bool) -> those keyword arguments.  Anything else: ValueError,
+    before anything runs on the device."""
+    cfg = getattr(model, "test_haarpsi", None)
+    if not cfg:
+        return None
+    if cfg is True:
+        return {}
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0          # noqa: E731
+    if (not isinstance(cfg, dict) or set(cfg) - {"c", "alpha", "subsample"} or not all(number(cfg[k]) for k in ("c", "alpha") if k in cfg)
+            or not isinstance(cfg.get("subsample", True), bool)):
+        raise ValueError(f"model.test_haarpsi: True or a dict with the keys c, alpha (positive numbers), subsample (a bool); got {cfg!r}")
+    return dict(cfg)
+
+
+def _haarpsi_update(triple, meters):
+    """The HaarPSI meters of one sample (after the sample's other keys); returns its CSV cell, the pred value."""
+    for who, v in zip(("input", "gt", "pred"), triple):
+        meters.setdefault(f"{who}_haarpsi", _Meter()).update(v, 1)
+    return (triple[2],)
+
+
 def _iqa_update(iqa, triples, meters):
     """The meters of one sample (after the sample's other keys); returns its CSV cells, the pred values."""
     for name, triple in zip(iqa, triples):
@@ -272,7 +295,7 @@ def _iqa_update(iqa, triples, meters):
     return tuple(t[2] for t in triples)
 
 
-def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa=None):
+def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa=None, haarpsi=None):
     """One loader batch of test_MTD_GAN_Ours under `model.test_per_slice`: B meter updates and B rows from one host read."""
     from . import kernels as K, metrics as M
     B, _, H, W = x.shape
@@ -285,12 +308,15 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
             rows_.append(f.float())
     if iqa is not None:
         parts.append(M.iqa_metrics_each(x, y, clipped, iqa).flatten())          # (metric, who, slice) float64, behind the others
+    if haarpsi is not None:
+        parts.append(M.haarpsi_each(x, y, clipped, **haarpsi).flatten())        # (who, slice) float64, behind the iqa block
     vals = torch.cat(parts).tolist()                  # every per-slice value of the batch in one device -> host copy
     l1 = vals[:B]
     sums = [[vals[B + (k * B + i) * 2:B + (k * B + i) * 2 + 2] for i in range(B)] for k in range(3)]
     six = [vals[7 * B + r * B:7 * B + (r + 1) * B] for r in range(6)] if vgg is not None else None
     pm = M._slice_triples(sums, H * W)
     q0 = (13 if vgg is not None else 7) * B           # where the iqa block starts
+    q1 = q0 + 3 * B * len(iqa or ())                  # where the HaarPSI block starts
     paths = batch_data.get("path_n_20") if isinstance(batch_data, dict) else None
     for i in range(B):
         meters.setdefault("L1_loss", _Meter()).update(l1[i], 1)
@@ -304,6 +330,8 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
             for who, v in zip(("input", "gt", "pred"), pm[name][i]):
                 meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
         more = _iqa_update(iqa, [tuple(vals[q0 + (r * 3 + k) * B + i] for k in range(3)) for r in range(len(iqa))], meters) if iqa is not None else ()
+        if haarpsi is not None:
+            more += _haarpsi_update(tuple(vals[q1 + k * B + i] for k in range(3)), meters)
         path = paths[i] if paths is not None else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][i][2], pm["psnr"][i][2], pm["ssim"][i][2]) + more)
 
@@ -488,6 +516,14 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     B values per slice travel in the batch's one device -> host copy.  Slices of at least 161 x 161 for MS-SSIM, 41 x 41 for
     VIFp (ValueError otherwise).  Any other value of the attribute is refused (ValueError) before anything runs; without it (or
     with a falsy value) nothing changes.
+    `model.test_haarpsi = True` (or `dict(c=..., alpha=..., subsample=...)`) adds the reference's vendored piq metric
+    HaarPSI (haarpsi with scales=3) of (input, gt, clipped prediction) against gt on the HIP kernels of csrc/haarpsi.hip
+    (metrics.haarpsi_each): the result gains input_haarpsi / gt_haarpsi / pred_haarpsi after the `test_iqa` keys (before the FID /
+    KID keys) and the CSV the column HaarPSI after the IQA columns, holding the prediction's value.  On the default path a batch
+    gives one value per image set (the mean over its slices, piq's reduction='mean', one more host read); under `test_per_slice`
+    the 3 B values travel in the batch's one device -> host copy, behind the IQA block.  Slices of at least 16 x 16 (ValueError
+    otherwise).  Any other value of the attribute -- a dict with other keys, a non-positive c or alpha, a subsample that is not a
+    bool -- is refused (ValueError) before anything runs; without it (or with a falsy value) nothing changes.
     `model.test_kid = True` (or a dict of metrics.kid_distance64's keyword arguments) adds piq's Kernel Inception
     Distance after the loop, from the same feature rows as FID and therefore only with `model.fid_features` (ValueError
     otherwise, before anything runs): the result gains input_kid / gt_kid / pred_kid behind the FID keys (metrics.compute_KID:
@@ -496,6 +532,7 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     draws them, three calls' worth in the order input, gt, pred.  The CSV does not change.  Without the attribute (or with a
     falsy value) nothing changes."""
     _iqa_option(model)                                   # (a bad value is refused before anything else is set up)
+    _haarpsi_option(model)
     _kid_option(model)
     stored = _StoredInput.from_model(model)
     dcm = _DcmSink.from_model(model, stored)
@@ -517,6 +554,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
     fid_features = getattr(model, "fid_features", None)
     per_slice = bool(getattr(model, "test_per_slice", False))
     iqa = _iqa_option(model)
+    haarpsi = _haarpsi_option(model)
     kid = _kid_option(model)
     feats = ([], [], [])
     meters = {}
@@ -541,7 +579,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         if dcm is not None:
             slices = dcm.begin(pred, words, table)             # likewise
         if per_slice:
-            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa)
+            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa, haarpsi)
             if png is not None:
                 png.submit(images, batch_data, k0)
             if dcm is not None:
@@ -567,6 +605,8 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         more = ()
         if iqa is not None:          # the batch is one sample: the mean over its slices, piq's reduction='mean' (one more host read)
             more = _iqa_update(iqa, M.iqa_metrics_each(x, y, clipped, iqa).mean(dim=2).tolist(), meters)
+        if haarpsi is not None:      # likewise
+            more += _haarpsi_update(tuple(M.haarpsi_each(x, y, clipped, **haarpsi).mean(dim=1).tolist()), meters)
         path = batch_data.get("path_n_20", [f"slice_{len(rows)}"])[0] if isinstance(batch_data, dict) else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]) + more)
         if png is not None:
@@ -578,7 +618,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         os.makedirs(save_dir, exist_ok=True)
         with open(os.path.join(save_dir, "pred_results.csv"), "w") as f:
             f.write((",PATH,PL,TML,RMSE,PSNR,SSIM" if vgg is not None else ",PATH,RMSE,PSNR,SSIM")
-                    + "".join("," + _IQA_COLUMNS[n] for n in iqa or ()) + "\n")
+                    + "".join("," + _IQA_COLUMNS[n] for n in iqa or ()) + (",HaarPSI" if haarpsi is not None else "") + "\n")
             for i, r in enumerate(rows):
                 f.write(f"{i}," + ",".join(str(v) for v in r) + "\n")
     if fid_features is not None:

@@ -25,7 +25,11 @@ and GMSD (gmsd.py: gmsd) -- image by image on the HIP kernels of csrc/iqa.hip (`
 iqa_metrics_per_slice and compute_MS_SSIM / compute_VIF / compute_GMSD (engine.test_MTD_GAN_Ours under `model.test_iqa`).
 
 KID (module/piq/kid.py, vendored by the reference beside fid.py) from the same (N, D) feature rows as FID, in float64 on the HIP
-kernels of csrc/kid.hip (`mtd_kid`): kid_distance64 / compute_KID (engine.test_MTD_GAN_Ours under `model.test_kid`)."""
+kernels of csrc/kid.hip (`mtd_kid`): kid_distance64 / compute_KID (engine.test_MTD_GAN_Ours under `model.test_kid`).
+
+HaarPSI (module/piq/haarpsi.py: haarpsi with scales=3), the Haar wavelet perceptual similarity index, image by image on the HIP
+kernels of csrc/haarpsi.hip (`mtd_haarpsi_each`): haarpsi_each / haarpsi_per_slice and compute_HaarPSI
+(engine.test_MTD_GAN_Ours under `model.test_haarpsi`)."""
 import numpy as np
 import torch
 
@@ -218,6 +222,56 @@ def compute_VIF(input, target, pred, data_range=1.0, sigma_n_sq=2.0):
 def compute_GMSD(input, target, pred, data_range=1.0):
     """piq's gmsd(a, target) likewise.  Sides of at least 2."""
     return _iqa_mean("gmsd", input, target, pred, data_range)
+
+
+# ================================================================================================ HaarPSI
+HAARPSI_MIN_SIDE = 16                                           # piq's own limit: 2 ** (scales + 1), checked before the subsampling
+
+
+def haarpsi_each(input, target, pred, c=30.0, alpha=4.2, subsample=True, parts=False):
+    """HaarPSI (piq's haarpsi with scales=3, data_range 1) of every slice of (input, target, pred) against the same slice of
+    target, without a host read: a (3, B) float64 device tensor.  With parts=True also the (3, B, 4) float64 sums: (num, den) of
+    the orientation of the Haar filter as it is, then of its transpose (num = sum sigmoid(alpha sim) w, den = sum w).  A slice's
+    values depend neither on the batch it is in nor on the other two image sets (mtd_haarpsi_each: fp32 filters; similarity,
+    sigmoid and per-image sums in double in a fixed order; two launches for the three pairs of the batch).  Two all-zero images
+    give +inf, as piq does.  Sides of at least 16, with subsample or without (ValueError, as piq raises)."""
+    for t in (input, target, pred):
+        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
+            raise AssertionError("haarpsi expects (B,1,H,W) tensors of the same shape")
+        if not t.is_cuda:
+            raise RuntimeError("haarpsi: HIP path needs CUDA tensors (no CPU fallback)")
+    B, _, H, W = target.shape
+    if H < HAARPSI_MIN_SIDE or W < HAARPSI_MIN_SIDE:
+        raise ValueError(f"haarpsi needs images of at least {HAARPSI_MIN_SIDE}x{HAARPSI_MIN_SIDE}, got {H}x{W}")
+    if not c > 0 or not alpha > 0:
+        raise ValueError(f"haarpsi: c and alpha must be positive, got {c!r}, {alpha!r}")
+    import ctypes
+    srcs = [t.contiguous().float() for t in (input, target, pred)]
+    sub = 1 if subsample else 0
+    L = _lib.lib()
+    dev = srcs[1].device
+    out = torch.empty((3, B), dtype=torch.float64, device=dev)
+    sums = torch.empty((3, B, 4), dtype=torch.float64, device=dev) if parts else None
+    ws = K.workspace(L.mtd_haarpsi_ws_bytes(3, B, H, W, sub), dev)
+    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    _lib.check(L.mtd_haarpsi_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, sub, float(c), float(alpha), out.data_ptr(),
+                                  sums.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_haarpsi_each")
+    return (out, sums) if parts else out
+
+
+def haarpsi_per_slice(input, target, pred, c=30.0, alpha=4.2, subsample=True):
+    """haarpsi_each as host numbers: a list of B (input, gt, pred) triples (the kernels' float64 scores).  One device -> host
+    copy for the batch."""
+    vals = haarpsi_each(input, target, pred, c, alpha, subsample).tolist()
+    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+
+
+def compute_HaarPSI(input, target, pred, data_range=1.0, **kw):
+    """piq's haarpsi(a, target) with its defaults (or c, alpha, subsample) for a = input, target, pred: (input, gt, pred) floats,
+    each the mean over the batch of the per-image scores (reduction='mean').  Sides of at least 16."""
+    if data_range != 1.0:
+        raise NotImplementedError("haarpsi: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
+    return tuple(haarpsi_each(input, target, pred, **kw).mean(dim=1).tolist())
 
 
 # ================================================================================================ perceptual metrics
