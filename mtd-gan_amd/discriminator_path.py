@@ -10,7 +10,6 @@ weight_orig in place and scale their accumulators by 1/sigma; the weight gradien
 """
 from . import _options
 import ctypes as C
-import os
 import re
 
 import torch
@@ -19,108 +18,84 @@ from . import _lib
 from . import kernels as K
 from .kernels import ACT_LRELU, ACT_NONE
 
-PS_FUSED = _options.lab("MTD_NO_PS_FUSE", "0") != "1"     # r_up{l}: conv1x1 + PixelShuffle as four strided-output classes in one grid
 CH = [64, 128, 256, 512, 512, 512]                    # trunk channels per level (out_channels = 64)
 DEC = [(1024, 512), (1024, 512), (1024, 256), (512, 128), (256, 64), (128, 1)]   # (cat channels, out) per decoder level
 RUP = [(512, 512), (512, 512), (512, 512), (256, 256), (128, 128), (64, 64)]      # r_up{l}: cin -> cout' (conv to 4*cout')
+HEAD = {"s": "dec_out", "r": "rec_out"}               # the 1x1 output conv of the pixel-level / the restoration decoder
 
 
-def sn_layer_specs():
-    """(name, rows, cols) of the 45 spectral-normalised layers in a fixed order."""
-    out = []
-    cin = 1
+def _layers():
+    """The one walk over the architecture: (name, N, C, kernel, stride, side of the input map, parameter suffix) of every conv
+    with a derived weight view or a spectral norm, in a fixed order -- trunk, bottleneck and image-level head, the two decoders,
+    the restoration decoder's 1x1 up-convs.  SN_SPECS and the three view lists below are filters over it."""
+    cin, r = 1, 64
     for l, co in enumerate(CH, start=1):
-        out.append((f"conv{l}1", co, cin * 9))
-        out.append((f"conv{l}2", co, co * 9))
-        out.append((f"down{l}", co, co * 16))
-        cin = co
-    out += [("bconv1", 512, 512), ("bconv2", 512, 512), ("c_fc", 512, 512)]
+        yield f"conv{l}1", co, cin, 3, 1, r, ".weight_orig"
+        yield f"conv{l}2", co, co, 3, 1, r, ".weight_orig"
+        yield f"down{l}", co, co, 4, 2, r, ".weight_orig"
+        cin, r = co, r // 2
+    for name in ("bconv1", "bconv2", "c_fc"):
+        yield name, 512, 512, 1, 1, 1, ".weight_orig"
     for pre in ("s", "r"):
         for l, (ci, co) in enumerate(DEC, start=1):
-            out.append((f"{pre}_dconv{l}1", co, ci * 9))
-            out.append((f"{pre}_dconv{l}2", co, co * 9))
-    return out
+            yield f"{pre}_dconv{l}1", co, ci, 3, 1, 2 ** l, ".weight_orig"
+            yield f"{pre}_dconv{l}2", co, co, 3, 1, 2 ** l, ".weight_orig"
+    for l, (ci, cu) in enumerate(RUP, start=1):
+        yield f"r_up{l}.upsample.0", 4 * cu, ci, 1, 1, 2 ** (l - 1), ".weight"
 
 
-SN_SPECS = sn_layer_specs()
+LAYERS = tuple(_layers())
+
+
+def _offsets(sizes):
+    """Exclusive prefix sums and the total."""
+    offs, total = [], 0
+    for n in sizes:
+        offs.append(total)
+        total += n
+    return offs, total
+
+
+# (name, rows, cols) of the 45 spectral-normalised layers and where each one's u, v and weight start in the flat buffers
+SN_SPECS = [(name, N, Cc * k * k) for name, N, Cc, k, _s, _r, suffix in LAYERS if suffix == ".weight_orig"]
 SN_INDEX = {n: i for i, (n, _, _) in enumerate(SN_SPECS)}
-SN_ROW_OFF, SN_COL_OFF = [], []
-_r = _c = 0
-for _n, _rows, _cols in SN_SPECS:
-    SN_ROW_OFF.append(_r)
-    SN_COL_OFF.append(_c)
-    _r += _rows
-    _c += _cols
-SN_ROWS_TOTAL, SN_COLS_TOTAL = _r, _c
-SN_W_OFF = []
-_o = 0
-for _n, _rows, _cols in SN_SPECS:
-    SN_W_OFF.append(_o)
-    _o += _rows * _cols
-SN_W_TOTAL = _o
+SN_ROW_OFF, SN_ROWS_TOTAL = _offsets(rows for _n, rows, _cols in SN_SPECS)
+SN_COL_OFF, SN_COLS_TOTAL = _offsets(cols for _n, _rows, cols in SN_SPECS)
+SN_W_OFF, SN_W_TOTAL = _offsets(rows * cols for _n, rows, cols in SN_SPECS)
+
+
+def _present(P):
+    """The layers of the table this discriminator has (the ablation subsets lack heads), each with its weight."""
+    for name, N, Cc, k, _s, r, suffix in LAYERS:
+        w = P.get(name + suffix)
+        if w is not None:
+            yield w, N, Cc, k, r
 
 
 def conv_views(P, backward):
     """Every implicit-GEMM weight view a discriminator pass (and its replay) will ask kernels.conv() for, so
     that they can be packed in one launch per optimizer step instead of one per layer."""
     v = []
-
-    def add(name, N, Cc, k, suffix=".weight_orig", r=0):
-        w = P.get(name + suffix)
-        if w is None:                                          # a head this discriminator does not have (ablation subsets)
-            return
+    for w, N, Cc, k, r in _present(P):
         # (3x3 layers on r x r maps that kernels.conv() sends to the Winograd kernel need no [tap][n][c] view: winograd_views)
-        if not (r and K.winograd_takes(K.geom_fwd(1, r, r, 3, 1, 1), N, Cc, {})):
+        if not (k == 3 and K.winograd_takes(K.geom_fwd(1, r, r, 3, 1, 1), N, Cc, {})):
             v.append((w, N, Cc, Cc * k * k, k * k))           # forward view (OIHW)
-        if backward and not (r and K.winograd_takes(K.geom_dgrad_s1(1, r, r, 3, 1), Cc, N, {})):
+        if backward and not (k == 3 and K.winograd_takes(K.geom_dgrad_s1(1, r, r, 3, 1), Cc, N, {})):
             v.append((w, Cc, N, k * k, Cc * k * k))           # data-gradient view (transposed)
-
-    cin, r = 1, 64
-    for l, co in enumerate(CH, start=1):
-        add(f"conv{l}1", co, cin, 3, r=r)
-        add(f"conv{l}2", co, co, 3, r=r)
-        add(f"down{l}", co, co, 4)
-        cin, r = co, r // 2
-    add("bconv1", 512, 512, 1)
-    add("bconv2", 512, 512, 1)
-    add("c_fc", 512, 512, 1)
-    for pre in ("s", "r"):
-        r = 2
-        for l, (ci, co) in enumerate(DEC, start=1):
-            add(f"{pre}_dconv{l}1", co, ci, 3, r=r)
-            add(f"{pre}_dconv{l}2", co, co, 3, r=r)
-            r *= 2
-    for l, (ci, cu) in enumerate(RUP, start=1):
-        add(f"r_up{l}.upsample.0", 4 * cu, ci, 1, ".weight")
     return v
 
 
 def winograd_views(P, backward):
-    """The 3x3 stride-1 layers whose maps are large enough for kernels.conv() to send them to the Winograd kernel
-    (kernels.winograd_takes), as (w, N, C, w_sn, w_sc, geometry) for kernels.prepack_winograd: their transformed weights are
+    """The 3x3 stride-1 layers as (w, N, C, w_sn, w_sc, geometry) for kernels.prepack_winograd, which keeps those whose maps are
+    large enough for kernels.conv() to send them to the Winograd kernel (kernels.winograd_takes): their transformed weights are
     then built in ONE launch per optimizer step.  The geometry only selects the tap order (forward / data gradient) and the
     size thresholds, so batch 1 stands in for the real batch."""
     v = []
-
-    def add(name, N, Cc, r):
-        w = P.get(name + ".weight_orig")
-        if w is None:
-            return
-        v.append((w, N, Cc, Cc * 9, 9, K.geom_fwd(1, r, r, 3, 1, 1)))
-        if backward:
-            v.append((w, Cc, N, 9, Cc * 9, K.geom_dgrad_s1(1, r, r, 3, 1)))
-
-    cin, r = 1, 64
-    for l, co in enumerate(CH, start=1):
-        add(f"conv{l}1", co, cin, r)
-        add(f"conv{l}2", co, co, r)
-        cin, r = co, r // 2
-    for pre in ("s", "r"):
-        r = 2
-        for l, (ci, co) in enumerate(DEC, start=1):
-            add(f"{pre}_dconv{l}1", co, ci, r)
-            add(f"{pre}_dconv{l}2", co, co, r)
-            r *= 2
+    for w, N, Cc, k, r in _present(P):
+        if k == 3:
+            v.append((w, N, Cc, Cc * 9, 9, K.geom_fwd(1, r, r, 3, 1, 1)))
+            if backward:
+                v.append((w, Cc, N, 9, Cc * 9, K.geom_dgrad_s1(1, r, r, 3, 1)))
     return v
 
 
@@ -129,17 +104,22 @@ def winograd_s2_views(P, backward):
     the data gradient) ask the F(3x3, 2x2) kernel's weights in, for kernels.prepack_winograd_s2 (which prepares the ones the
     step really uses).  The geometry only selects the filter entries, so batch 1 stands in for the real batch."""
     v = []
-    r = 64
-    for l, co in enumerate(CH, start=1):
-        w = P.get(f"down{l}.weight_orig")
-        if w is not None and r // 2 >= K.WINO_S2_MIN_HW:
-            v.append((w, co, co, co * 16, 16, K.geom_fwd(1, r, r, 4, 2, 1)))
+    for w, N, Cc, k, r in _present(P):
+        if k == 4 and r // 2 >= K.WINO_S2_MIN_HW:
+            v.append((w, N, Cc, Cc * 16, 16, K.geom_fwd(1, r, r, 4, 2, 1)))
             if backward:
-                for py in range(2):
-                    for px in range(2):
-                        v.append((w, co, co, 16, co * 16, K.geom_dgrad_s2(1, r, r, py, px)))
-        r //= 2
+                v.extend((w, Cc, N, 16, Cc * 16, K.geom_dgrad_s2(1, r, r, py, px)) for py in range(2) for px in range(2))
     return v
+
+
+def prepack_views(P, backward, keep=None):
+    """Every derived weight view of a pass in three launches: [tap][n][c], Winograd and F(3x3, 2x2).  keep: a predicate on the
+    parameter name -- the views of those weights alone (the two ranges of the D-to-G hand-over)."""
+    if keep is not None:
+        P = {n: w for n, w in P.items() if keep(n)}
+    K.prepack(conv_views(P, backward))
+    K.prepack_winograd(winograd_views(P, backward))
+    K.prepack_winograd_s2(winograd_s2_views(P, backward))
 
 
 class DiscRuntime:
@@ -164,7 +144,36 @@ class Tape:
 
 SN_MERGE_HALVES = _options.lab("MTD_SN_MERGE_HALVES", "1") != "0"      # ... and both halves of a paired pass in one small-map weight-gradient launch
 SN_ACT_DOT = _options.lab("MTD_SN_ACT_DOT", "1") != "0"        # the spectral-norm correction's <G, W> from (cotangent, saved output) on the small maps (round 6)
-SKIP_IN_CAT = _options.lab("MTD_SKIP_IN_CAT", "1") != "0"      # trunk outputs written into the pixel-level decoder's concatenated buffers
+
+
+def _sn_alloc(device):
+    """The result of one power iteration over all layers: (sig[45,2], u_save, v_save)."""
+    return (torch.empty((len(SN_SPECS), 2), dtype=torch.float32, device=device),
+            torch.empty(SN_ROWS_TOTAL, dtype=torch.float32, device=device),
+            torch.empty(SN_COLS_TOTAL, dtype=torch.float32, device=device))
+
+
+def _sn_slots(i, sn):
+    """Where layer i's (sigma, 1 / sigma), u and v stand in such a result: three addresses."""
+    sig, u_save, v_save = sn
+    return sig.data_ptr() + 8 * i, u_save.data_ptr() + 4 * SN_ROW_OFF[i], v_save.data_ptr() + 4 * SN_COL_OFF[i]
+
+
+def _sn_layers(P, sn, only=None):
+    """The SnLayer descriptors of one power iteration into `sn`, for the layers this discriminator has (ablation subsets: an
+    absent layer's sigma slot stays unused) and `only` selects."""
+    structs = []
+    for i, (n, rows, cols) in enumerate(SN_SPECS):
+        if n + ".weight_orig" not in P or (only is not None and not only(n)):
+            continue
+        s = _lib.SnLayer()
+        s.w = P[n + ".weight_orig"].data_ptr()
+        s.u = P[n + ".weight_u"].data_ptr()
+        s.v = P[n + ".weight_v"].data_ptr()
+        s.sigma, s.u_save, s.v_save = _sn_slots(i, sn)
+        s.rows, s.cols = rows, cols
+        structs.append(s)
+    return structs
 
 
 def _sn_forward(P, train, device, only=None, out=None):
@@ -172,33 +181,15 @@ def _sn_forward(P, train, device, only=None, out=None):
     only: a predicate on the layer name -- the launches cover those layers alone; out: the three tensors of an earlier call,
     filled in for these layers (the layers are independent: a pass in two ranges gives what one pass gives)."""
     L = _lib.lib()
-    if out is not None:
-        sig, u_save, v_save = out
-    else:
-        sig = torch.empty((len(SN_SPECS), 2), dtype=torch.float32, device=device)
-        u_save = torch.empty(SN_ROWS_TOTAL, dtype=torch.float32, device=device)
-        v_save = torch.empty(SN_COLS_TOTAL, dtype=torch.float32, device=device)
-    structs = []
-    for i, (n, rows, cols) in enumerate(SN_SPECS):
-        if n + ".weight_orig" not in P or (only is not None and not only(n)):     # ablation subsets: no such layer, its sigma slot stays unused
-            continue
-        s = _lib.SnLayer()
-        s.w = P[n + ".weight_orig"].data_ptr()
-        s.u = P[n + ".weight_u"].data_ptr()
-        s.v = P[n + ".weight_v"].data_ptr()
-        s.sigma = sig.data_ptr() + 8 * i
-        s.u_save = u_save.data_ptr() + 4 * SN_ROW_OFF[i]
-        s.v_save = v_save.data_ptr() + 4 * SN_COL_OFF[i]
-        s.rows, s.cols = rows, cols
-        structs.append(s)
-    if not structs:
-        return sig, u_save, v_save
-    dev_tab, host_arr = K.device_table(structs, device)
-    need = L.mtd_sn_ws_bytes(C.cast(host_arr, C.c_void_p), len(structs))
-    ws = K.workspace(need, device)
-    K.check(L.mtd_sn_power_iter(dev_tab.data_ptr(), C.cast(host_arr, C.c_void_p), len(structs), 1 if train else 0, ws.data_ptr(),
-                                K.stream_ptr()), "mtd_sn_power_iter")
-    return sig, u_save, v_save
+    sn = out if out is not None else _sn_alloc(device)
+    structs = _sn_layers(P, sn, only)
+    if structs:
+        dev_tab, host_arr = K.device_table(structs, device)
+        need = L.mtd_sn_ws_bytes(C.cast(host_arr, C.c_void_p), len(structs))
+        ws = K.workspace(need, device)
+        K.check(L.mtd_sn_power_iter(dev_tab.data_ptr(), C.cast(host_arr, C.c_void_p), len(structs), 1 if train else 0, ws.data_ptr(),
+                                    K.stream_ptr()), "mtd_sn_power_iter")
+    return sn
 
 
 # ---- the D-to-G hand-over in two ranges (train_step.d_optimizer_step).  The optimizer launch of the "deep" layers -- everything
@@ -213,6 +204,10 @@ _tail_pending = {}       # device index -> True while a deep range's optimizer l
 def is_shallow(name):
     """Does this parameter / layer name (state_dict style, with or without a suffix) belong to trunk levels 1-3?"""
     return _SHALLOW.match(name + ".") is not None
+
+
+def _is_deep(name):
+    return not is_shallow(name)
 
 
 def tail_on_side(device):
@@ -237,24 +232,8 @@ def _sn_forward_multi(P, train, device, nit):
     if not (train and SN_FUSED_ITERS and nit > 1):
         return [_sn_forward(P, train, device) for _ in range(nit)]
     L = _lib.lib()
-    outs, structs = [], []
-    for _it in range(nit):
-        sig = torch.empty((len(SN_SPECS), 2), dtype=torch.float32, device=device)
-        u_save = torch.empty(SN_ROWS_TOTAL, dtype=torch.float32, device=device)
-        v_save = torch.empty(SN_COLS_TOTAL, dtype=torch.float32, device=device)
-        outs.append((sig, u_save, v_save))
-        for i, (n, rows, cols) in enumerate(SN_SPECS):
-            if n + ".weight_orig" not in P:
-                continue
-            s = _lib.SnLayer()
-            s.w = P[n + ".weight_orig"].data_ptr()
-            s.u = P[n + ".weight_u"].data_ptr()
-            s.v = P[n + ".weight_v"].data_ptr()
-            s.sigma = sig.data_ptr() + 8 * i
-            s.u_save = u_save.data_ptr() + 4 * SN_ROW_OFF[i]
-            s.v_save = v_save.data_ptr() + 4 * SN_COL_OFF[i]
-            s.rows, s.cols = rows, cols
-            structs.append(s)
+    outs = [_sn_alloc(device) for _ in range(nit)]
+    structs = [s for sn in outs for s in _sn_layers(P, sn)]
     n_layers = len(structs) // nit
     dev_tab, host_arr = K.device_table(structs, device)
     need = L.mtd_sn_ws_bytes(C.cast(host_arr, C.c_void_p), n_layers)
@@ -264,18 +243,13 @@ def _sn_forward_multi(P, train, device, nit):
     return outs
 
 
-def _inv_sigma(tape, name):
-    i = SN_INDEX[name]
-    return tape.sig[i, 1:2]
-
-
 def _scales(tape, name, geom):
     """Accumulator scale(s) 1/sigma of an SN layer for a launch with geometry `geom`: a paired tape (two passes stacked along
     the batch, each with its own power-iteration state) switches to the second pass's 1/sigma at its first pixel."""
     i = SN_INDEX[name]
-    kw = {"scale": tape.sig[i, 1:2]}
-    if getattr(tape, "pair", 0):
-        kw["scale2"] = tape.sig2[i, 1:2]
+    kw = {"scale": tape.sn[0][i, 1:2]}
+    if tape.pair:
+        kw["scale2"] = tape.sn2[0][i, 1:2]
         kw["scale_split"] = tape.pair * geom.OH * geom.OW
     return kw
 
@@ -296,6 +270,56 @@ def _sn_conv(P, tape, name, x, out, geom, N, Cc, k, act):
 PAIR_DECODERS = _options.lab("MTD_PAIR_DECODERS", "1") != "0"
 
 
+def _decoders_forward(P, tp, x, decs, seg_cat):
+    """The decoders in `decs` -- ("s", "r") level by level with their mirror convs in pairs, or one of them alone -- from the
+    bottleneck to their 1x1 output convs (networks.py:420-467).  Fills tp.dec[pre][level] = (input, concatenated buffer, first
+    conv's output, second conv's output) and returns the decoders' outputs in the order of `decs`."""
+    B = tp.B
+    t = {pre: tp.bot for pre in decs}
+    for pre in decs:
+        tp.dec[pre] = {}
+    for lvl in range(1, 7):
+        r = 2 ** lvl
+        skip = tp.xs[7 - lvl]
+        ccat, co = DEC[lvl - 1]
+        cat = {}
+        for pre in decs:
+            if pre == "s":
+                cat[pre] = seg_cat[lvl]                       # (the skip half is there already: disc_forward's trunk)
+                K.upsample2x_fwd(t[pre], cat[pre][..., :t[pre].shape[3]])
+            else:
+                # conv1x1 (C -> 4C') + PixelShuffle(2) without the intermediate tensor: the four sub-pixel classes (i, j) are four
+                # 1x1 convs over output channels c*4 + 2i + j (weight rows 4 apart) that write every other pixel of the
+                # concatenated buffer -- one grid (conv_multi), like the parity classes of the stride-2 data gradients
+                cin_up, cup = RUP[lvl - 1]
+                cat[pre] = K.empty_nhwc(B, r, r, ccat, x)
+                bu = K.regrouped_bias(P[f"r_up{lvl}.upsample.0.bias"], 4)
+                wq = P[f"r_up{lvl}.upsample.0.weight"].detach().view(cup, 4, cin_up)
+                K.conv_multi([((t[pre], wq[:, q], K.geom_pixel_shuffle2(B, r // 2, r // 2, q >> 1, q & 1), cup, cin_up, 4 * cin_up, 1,
+                                cat[pre][..., :cup]), dict(bias=bu[q * cup:(q + 1) * cup])) for q in range(4)])
+                K.copy_channels(skip, cat[pre][..., cup:])
+        g3 = K.geom_fwd(B, r, r, 3, 1, 1)
+        src, outs = cat, [cat]
+        for j, cin in ((1, ccat), (2, co)):
+            out = {pre: K.empty_nhwc(B, r, r, co, x) for pre in decs}
+            calls = [_sn_call(P, tp, f"{pre}_dconv{lvl}{j}", src[pre], out[pre], g3, co, cin, 3, ACT_LRELU) for pre in decs]
+            if len(calls) == 2:
+                K.conv_pair(*calls)
+            else:
+                K.conv(*calls[0][0], **calls[0][1])
+            src = out
+            outs.append(out)
+        for pre in decs:
+            tp.dec[pre][lvl] = (t[pre],) + tuple(o[pre] for o in outs)
+        t = src
+    g64 = K.geom_fwd(B, 64, 64, 1, 1, 0)
+    res = []
+    for pre in decs:
+        res.append(K.empty_nhwc(B, 64, 64, 1, x))
+        K.conv(t[pre], P[HEAD[pre] + ".weight"], g64, 1, 1, 1, 1, res[-1], bias=P[HEAD[pre] + ".bias"])
+    return res
+
+
 def disc_forward(P, x, train, drop_mask, need_rec, save, sn=None, sn2=None, pair=0, heads=("cls", "seg", "rec")):
     """x: (B,64,64,1) NHWC.  P: dict name -> tensor (reference state_dict names).  drop_mask: (B,512)
     multiplier or None.  Returns ((enc (B,1,1,1), dec (B,64,64,1), rec or None), tape).
@@ -312,33 +336,22 @@ def disc_forward(P, x, train, drop_mask, need_rec, save, sn=None, sn2=None, pair
     split = sn is None and _tail_pending.get(dev.index if dev.index is not None else torch.cuda.current_device(), False)
     if not split:
         settle_tail(dev)
-        K.prepack(conv_views(P, save))
-        K.prepack_winograd(winograd_views(P, save))
-        K.prepack_winograd_s2(winograd_s2_views(P, save))
-        tp.sig, tp.u_save, tp.v_save = sn if sn is not None else _sn_forward(P, train, dev)
+        prepack_views(P, save)
+        tp.sn = sn if sn is not None else _sn_forward(P, train, dev)
     else:
         # levels 1-3 here; the rest behind its optimizer launch on the side stream, joined at conv41 below
-        shallow_w = {id(P[k]) for k in P if is_shallow(k)}
-        deep_sn = lambda n: not is_shallow(n)
-        cv, wv, sv = conv_views(P, save), winograd_views(P, save), winograd_s2_views(P, save)
-        K.prepack([v for v in cv if id(v[0]) in shallow_w])
-        K.prepack_winograd([v for v in wv if id(v[0]) in shallow_w])
-        K.prepack_winograd_s2([v for v in sv if id(v[0]) in shallow_w])
-        tp.sig, tp.u_save, tp.v_save = out = _sn_forward(P, train, dev, only=is_shallow)
+        prepack_views(P, save, keep=is_shallow)
+        tp.sn = _sn_forward(P, train, dev, only=is_shallow)
 
         def deep_range():
-            K.prepack([v for v in cv if id(v[0]) not in shallow_w])
-            K.prepack_winograd([v for v in wv if id(v[0]) not in shallow_w])
-            K.prepack_winograd_s2([v for v in sv if id(v[0]) not in shallow_w])
-            _sn_forward(P, train, dev, only=deep_sn, out=out)
+            prepack_views(P, save, keep=_is_deep)
+            _sn_forward(P, train, dev, only=_is_deep, out=tp.sn)
         K.side_stream(dev).run(deep_range, fork=False)          # (the stream holds this range's update; nothing of the main stream's is read)
-    tp.pair = int(pair)
-    if tp.pair:
-        if sn is None or sn2 is None or not (0 < tp.pair < B):
-            raise ValueError("paired discriminator pass needs both power-iteration states and 0 < pair < batch")
-        tp.sig2, tp.u_save2, tp.v_save2 = sn2
+    tp.pair, tp.sn2 = int(pair), sn2
+    if tp.pair and (sn is None or sn2 is None or not (0 < tp.pair < B)):
+        raise ValueError("paired discriminator pass needs both power-iteration states and 0 < pair < batch")
     tp.x_in, tp.B, tp.drop_mask, tp.need_rec = x, B, drop_mask, need_rec
-    tp.tin, tp.a, tp.xs = {}, {}, {}
+    tp.tin, tp.a, tp.xs, tp.dec = {}, {}, {}, {}
     t, h, cin = x, 64, 1
     # A trunk level's output is the skip operand of BOTH decoders' level 7 - l (networks.py:420-467: torch.cat([up, skip], 1)).  It is
     # written straight into the channel slice [ccat - co, ccat) of the pixel-level decoder's concatenated buffer (every kernel takes a
@@ -350,7 +363,7 @@ def disc_forward(P, x, train, drop_mask, need_rec, save, sn=None, sn2=None, pair
         g3 = K.geom_fwd(B, h, h, 3, 1, 1)
         a = K.empty_nhwc(B, h, h, co, x)
         _sn_conv(P, tp, f"conv{l}1", t, a, g3, co, cin, 3, ACT_LRELU)
-        if SKIP_IN_CAT and "seg" in heads:
+        if "seg" in heads:
             ccat = DEC[6 - l][0]
             seg_cat[7 - l] = K.empty_nhwc(B, h, h, ccat, x)
             xl = seg_cat[7 - l][..., ccat - co:]
@@ -375,110 +388,12 @@ def disc_forward(P, x, train, drop_mask, need_rec, save, sn=None, sn2=None, pair
         tp.cm = K.mul(tp.c, drop_mask.reshape(B, 1, 1, 512)) if drop_mask is not None else tp.c
         enc = K.empty_nhwc(B, 1, 1, 1, x)
         K.conv(tp.cm, P["enc_out.weight"], g1, 1, 512, 512, 1, enc, bias=P["enc_out.bias"])
-    # ---- both decoders level by level, their mirror convs in pairs (PAIR_DECODERS)
-    both = PAIR_DECODERS and "seg" in heads and need_rec and "rec" in heads
-    g64 = K.geom_fwd(B, 64, 64, 1, 1, 0)
-    if both:
-        tp.s_cat, tp.s_o1, tp.s_o2, tp.s_in = {}, {}, {}, {}
-        tp.r_cat, tp.r_o1, tp.r_o2, tp.r_in = {}, {}, {}, {}
-        ts, tr, r = tp.bot, tp.bot, 1
-        for lvl in range(1, 7):
-            skip = tp.xs[7 - lvl]
-            ccat, co = DEC[lvl - 1]
-            cprev = ts.shape[3]
-            cat_s = seg_cat.get(lvl)
-            if cat_s is None:
-                cat_s = K.empty_nhwc(B, 2 * r, 2 * r, ccat, x)
-                K.copy_channels(skip, cat_s[..., cprev:])
-            K.upsample2x_fwd(ts, cat_s[..., :cprev])
-            cin_up, cup = RUP[lvl - 1]
-            cat_r = K.empty_nhwc(B, 2 * r, 2 * r, ccat, x)
-            wu = P[f"r_up{lvl}.upsample.0.weight"]
-            if PS_FUSED:
-                bu = K.regrouped_bias(P[f"r_up{lvl}.upsample.0.bias"], 4)
-                wq = wu.detach().view(cup, 4, cin_up)
-                K.conv_multi([((tr, wq[:, q], K.geom_pixel_shuffle2(B, r, r, q >> 1, q & 1), cup, cin_up, 4 * cin_up, 1, cat_r[..., :cup]),
-                               dict(bias=bu[q * cup:(q + 1) * cup])) for q in range(4)])
-            else:
-                up = K.empty_nhwc(B, r, r, 4 * cup, x)
-                K.conv(tr, wu, K.geom_fwd(B, r, r, 1, 1, 0), 4 * cup, cin_up, cin_up, 1, up, bias=P[f"r_up{lvl}.upsample.0.bias"])
-                K.pixel_shuffle2_fwd(up, cat_r[..., :cup])
-            K.copy_channels(skip, cat_r[..., cup:])
-            r *= 2
-            g3 = K.geom_fwd(B, r, r, 3, 1, 1)
-            o1s, o1r = K.empty_nhwc(B, r, r, co, x), K.empty_nhwc(B, r, r, co, x)
-            K.conv_pair(_sn_call(P, tp, f"s_dconv{lvl}1", cat_s, o1s, g3, co, ccat, 3, ACT_LRELU),
-                        _sn_call(P, tp, f"r_dconv{lvl}1", cat_r, o1r, g3, co, ccat, 3, ACT_LRELU))
-            o2s, o2r = K.empty_nhwc(B, r, r, co, x), K.empty_nhwc(B, r, r, co, x)
-            K.conv_pair(_sn_call(P, tp, f"s_dconv{lvl}2", o1s, o2s, g3, co, co, 3, ACT_LRELU),
-                        _sn_call(P, tp, f"r_dconv{lvl}2", o1r, o2r, g3, co, co, 3, ACT_LRELU))
-            tp.s_in[lvl], tp.s_cat[lvl], tp.s_o1[lvl], tp.s_o2[lvl] = ts, cat_s, o1s, o2s
-            tp.r_in[lvl], tp.r_cat[lvl], tp.r_o1[lvl], tp.r_o2[lvl] = tr, cat_r, o1r, o2r
-            ts, tr = o2s, o2r
-        dec = K.empty_nhwc(B, 64, 64, 1, x)
-        K.conv(ts, P["dec_out.weight"], g64, 1, 1, 1, 1, dec, bias=P["dec_out.bias"])
-        rec = K.empty_nhwc(B, 64, 64, 1, x)
-        K.conv(tr, P["rec_out.weight"], g64, 1, 1, 1, 1, rec, bias=P["rec_out.bias"])
-        return (enc, dec, rec), (tp if save else None)
-    # ---- SEG decoder (networks.py:420-442)
-    tp.s_cat, tp.s_o1, tp.s_o2, tp.s_in = {}, {}, {}, {}
-    t, r = tp.bot, 1
-    for lvl in range(1, 7) if "seg" in heads else ():
-        r *= 2
-        cprev = t.shape[3]
-        skip = tp.xs[7 - lvl]
-        ccat, co = DEC[lvl - 1]
-        cat = seg_cat.get(lvl)
-        if cat is None:
-            cat = K.empty_nhwc(B, r, r, ccat, x)
-            K.copy_channels(skip, cat[..., cprev:])
-        K.upsample2x_fwd(t, cat[..., :cprev])
-        g3 = K.geom_fwd(B, r, r, 3, 1, 1)
-        o1 = K.empty_nhwc(B, r, r, co, x)
-        _sn_conv(P, tp, f"s_dconv{lvl}1", cat, o1, g3, co, ccat, 3, ACT_LRELU)
-        o2 = K.empty_nhwc(B, r, r, co, x)
-        _sn_conv(P, tp, f"s_dconv{lvl}2", o1, o2, g3, co, co, 3, ACT_LRELU)
-        tp.s_in[lvl], tp.s_cat[lvl], tp.s_o1[lvl], tp.s_o2[lvl] = t, cat, o1, o2
-        t = o2
-    dec = None
-    if "seg" in heads:
-        dec = K.empty_nhwc(B, 64, 64, 1, x)
-        K.conv(t, P["dec_out.weight"], g64, 1, 1, 1, 1, dec, bias=P["dec_out.bias"])
-    # ---- REC decoder (networks.py:445-467)
-    rec = None
-    if need_rec and "rec" in heads:
-        tp.r_cat, tp.r_o1, tp.r_o2, tp.r_in = {}, {}, {}, {}
-        t, r = tp.bot, 1
-        for lvl in range(1, 7):
-            cin_up, cup = RUP[lvl - 1]
-            skip = tp.xs[7 - lvl]
-            ccat, co = DEC[lvl - 1]
-            cat = K.empty_nhwc(B, 2 * r, 2 * r, ccat, x)
-            # conv1x1 (C -> 4C') + PixelShuffle(2) without the intermediate tensor: the four sub-pixel classes (i, j) are four
-            # 1x1 convs over output channels c*4 + 2i + j (weight rows 4 apart) that write every other pixel of the
-            # concatenated buffer -- one grid (conv_multi), like the parity classes of the stride-2 data gradients
-            wu = P[f"r_up{lvl}.upsample.0.weight"]
-            if PS_FUSED:
-                bu = K.regrouped_bias(P[f"r_up{lvl}.upsample.0.bias"], 4)
-                wq = wu.detach().view(cup, 4, cin_up)
-                K.conv_multi([((t, wq[:, q], K.geom_pixel_shuffle2(B, r, r, q >> 1, q & 1), cup, cin_up, 4 * cin_up, 1, cat[..., :cup]),
-                               dict(bias=bu[q * cup:(q + 1) * cup])) for q in range(4)])
-            else:
-                up = K.empty_nhwc(B, r, r, 4 * cup, x)
-                K.conv(t, wu, K.geom_fwd(B, r, r, 1, 1, 0), 4 * cup, cin_up, cin_up, 1, up, bias=P[f"r_up{lvl}.upsample.0.bias"])
-                K.pixel_shuffle2_fwd(up, cat[..., :cup])
-            r *= 2
-            K.copy_channels(skip, cat[..., cup:])
-            g3 = K.geom_fwd(B, r, r, 3, 1, 1)
-            o1 = K.empty_nhwc(B, r, r, co, x)
-            _sn_conv(P, tp, f"r_dconv{lvl}1", cat, o1, g3, co, ccat, 3, ACT_LRELU)
-            o2 = K.empty_nhwc(B, r, r, co, x)
-            _sn_conv(P, tp, f"r_dconv{lvl}2", o1, o2, g3, co, co, 3, ACT_LRELU)
-            tp.r_in[lvl], tp.r_cat[lvl], tp.r_o1[lvl], tp.r_o2[lvl] = t, cat, o1, o2
-            t = o2
-        rec = K.empty_nhwc(B, 64, 64, 1, x)
-        K.conv(t, P["rec_out.weight"], g64, 1, 1, 1, 1, rec, bias=P["rec_out.bias"])
-    return (enc, dec, rec), (tp if save else None)
+    # ---- the decoders this pass runs: both together, their mirror convs in pairs (PAIR_DECODERS), else one after the other
+    decs = tuple(pre for pre, wanted in (("s", "seg" in heads), ("r", need_rec and "rec" in heads)) if wanted)
+    out = {}
+    for group in ([decs] if PAIR_DECODERS and len(decs) == 2 else [(pre,) for pre in decs]):
+        out.update(zip(group, _decoders_forward(P, tp, x, group, seg_cat)))
+    return (enc, out.get("s"), out.get("r")), (tp if save else None)
 
 
 class GradSink:
@@ -585,7 +500,7 @@ def _disc_backward_gen(rt, P, tp, g_enc, g_dec, g_rec, sink, want_input_grad, de
     def want(name):
         return sink is not None and sink.get(name) is not None
 
-    Bh = getattr(tp, "pair", 0)
+    Bh = tp.pair
     in_decoder = [False]
 
     def cot(key, p):
@@ -629,7 +544,7 @@ def _disc_backward_gen(rt, P, tp, g_enc, g_dec, g_rec, sink, want_input_grad, de
                     # the temp holds G_1 / sigma_1 + G_2 / sigma_2 and the correction adds two rank-one terms (its dot products come from
                     # the activation side: the raw gradients do not exist apart any more)
                     i = SN_INDEX[name]
-                    half = (tp.sig[i, 1:2], tp.sig2[i, 1:2], m_first)
+                    half = (tp.sn[0][i, 1:2], tp.sn2[0][i, 1:2], m_first)
                     side.run(lambda: K.wgrad(src(), q, gfull, N, Cc, rt.gtemp(name, dev, 2 * lane), Cc * k * k, k * k, db=sink.get(bn),
                                              accumulate=False, accumulate_bias=True, half=half), p, q)
                     sn_pre.add(name)
@@ -655,7 +570,6 @@ def _disc_backward_gen(rt, P, tp, g_enc, g_dec, g_rec, sink, want_input_grad, de
         return ((gpre, P[name + ".weight_orig"], gd, N, Cc, k * k, N * k * k, out),
                 dict(add1=add1, mask=mask, mask_slope=0.2, **_scales(tp, name, gd)))
 
-
     def sn_fix():
         """Corrects and accumulates the raw weight gradients taken since the last call (one launch, on the side stream:
         the stream of the weight gradients it corrects; callers join() before reading the sink)."""
@@ -668,9 +582,7 @@ def _disc_backward_gen(rt, P, tp, g_enc, g_dec, g_rec, sink, want_input_grad, de
             s = _lib.SnGradLayer()
             s.G = rt.gtemp(name, dev, 2 * lane).data_ptr()
             s.w = P[name + ".weight_orig"].data_ptr()
-            s.u = tp.u_save.data_ptr() + 4 * SN_ROW_OFF[i]
-            s.v = tp.v_save.data_ptr() + 4 * SN_COL_OFF[i]
-            s.sigma = tp.sig.data_ptr() + 8 * i
+            s.sigma, s.u, s.v = _sn_slots(i, tp.sn)
             s.g_out = sink.get(name + ".weight_orig").data_ptr()
             s.rows, s.cols, s.accumulate = SN_SPECS[i][1], SN_SPECS[i][2], 0 if name in overwrite else 1
             if Bh:      # the second half's own sigma, u, v: corrected and added in the same launch, after the first
@@ -678,24 +590,22 @@ def _disc_backward_gen(rt, P, tp, g_enc, g_dec, g_rec, sink, want_input_grad, de
                     s.prescaled = 1                  # (one gradient, already over both sigmas: wgrad_sn)
                 else:
                     s.G2 = rt.gtemp(name, dev, 2 * lane + 1).data_ptr()
-                s.u2 = tp.u_save2.data_ptr() + 4 * SN_ROW_OFF[i]
-                s.v2 = tp.v_save2.data_ptr() + 4 * SN_COL_OFF[i]
-                s.sigma2 = tp.sig2.data_ptr() + 8 * i
+                s.sigma2, s.u2, s.v2 = _sn_slots(i, tp.sn2)
             act = sn_act.pop(name, None)
             if act is not None:
                 pe, pe2, yout, inv_slope = act
-                if True:
-                    npix = pe.shape[0] * pe.shape[1] * pe.shape[2]
-                    s.act_gy, s.act_gy_ld = pe.data_ptr(), K.ld_of(pe)
-                    if pe2 is not None:
-                        s.act_gy2, s.act_gy2_ld = pe2.data_ptr(), K.ld_of(pe2)
-                    s.act_a, s.act_a_ld = yout.data_ptr(), K.ld_of(yout)
-                    s.act_bias = P[name + ".bias"].data_ptr()
-                    s.act_M, s.act_M_first, s.act_inv_slope = npix, (Bh * (npix // B) if Bh else npix), inv_slope
-                    held.extend(t for t in (pe, pe2, yout) if t is not None)
+                npix = pe.shape[0] * pe.shape[1] * pe.shape[2]
+                s.act_gy, s.act_gy_ld = pe.data_ptr(), K.ld_of(pe)
+                if pe2 is not None:
+                    s.act_gy2, s.act_gy2_ld = pe2.data_ptr(), K.ld_of(pe2)
+                s.act_a, s.act_a_ld = yout.data_ptr(), K.ld_of(yout)
+                s.act_bias = P[name + ".bias"].data_ptr()
+                s.act_M, s.act_M_first, s.act_inv_slope = npix, (Bh * (npix // B) if Bh else npix), inv_slope
+                held.extend(t for t in (pe, pe2, yout) if t is not None)
             structs.append(s)
         del sn_touched[:]
         sn_pre.clear()
+
         def fix():
             # (the descriptor table is built HERE, under the side stream: a new table's upload is then ordered before its reader
             # by the stream itself)
@@ -718,113 +628,70 @@ def _disc_backward_gen(rt, P, tp, g_enc, g_dec, g_rec, sink, want_input_grad, de
     g1 = K.geom_fwd(B, 1, 1, 1, 1, 0)
     g64 = K.geom_fwd(B, 64, 64, 1, 1, 0)
 
-    def decoder_backward(pre, g_out, cats, o1s, o2s, ins, head):
-        """shared by the SEG ('s') and REC ('r') decoders; returns the gradient of x_bot (a generator like its caller: the data
-        gradients of its 3x3 layers are handed out)"""
-        t6 = o2s[6]
+    def decoders_backward(decs):
+        """The decoders in `decs` from their output cotangents down to the bottleneck, level by level: ("r", "s") together, the data
+        gradients of their mirror convs in pairs (kernels.conv_pair), or one decoder alone, whose data gradients are handed out (a
+        generator like its caller).  Whatever else a level issues goes out per decoder in the order of `decs`.  Returns the gradients
+        of x_bot in that order."""
         in_decoder[0] = True
-        if want(head + ".weight"):
-            src_h = cot(head, g_out)
-            if src_h is not None:
-                side.run(lambda: K.wgrad(src_h(), t6, g64, 1, 1, sink.get(head + ".weight"), 1, 1, db=sink.get(head + ".bias"), accumulate=True), g_out, t6)
-        # every cotangent that reaches a level's second conv is multiplied by that conv's LeakyReLU gradient; the producer of the
-        # cotangent (head conv, upsampling adjoint, 1x1 up-conv data gradient) applies it in its epilogue instead of a pass of its own
-        g = K.empty_nhwc(B, 64, 64, 1, x)
-        K.conv(g_out, P[head + ".weight"], g64, 1, 1, 1, 1, g, mask=o2s[6], mask_slope=0.2)
-        for lvl in range(6, 0, -1):
-            r = 2 ** lvl
-            ccat, co = DEC[lvl - 1]
-            o2, o1, cat, tin = o2s[lvl], o1s[lvl], cats[lvl], ins[lvl]
-            g3 = K.geom_fwd(B, r, r, 3, 1, 1)
-            gpre2 = g                                      # already times (o2 > 0 ? 1 : 0.2)
-            below = o2s[lvl - 1] if lvl > 1 else None      # output of the level below (None: the bottleneck, masked by the caller)
-            wgrad_sn(f"{pre}_dconv{lvl}2", gpre2, o1, (r, 3, 1, 1), co, co, 3, yout=o2)
-            gpre1 = K.empty_nhwc(B, r, r, co, x)
-            yield dgrad_s1_call(f"{pre}_dconv{lvl}2", gpre2, r, co, co, gpre1, mask=o1)
-            wgrad_sn(f"{pre}_dconv{lvl}1", gpre1, cat, (r, 3, 1, 1), co, ccat, 3, yout=o1)
-            gcat = K.empty_nhwc(B, r, r, ccat, x)
-            yield dgrad_s1_call(f"{pre}_dconv{lvl}1", gpre1, r, ccat, co, gcat)
-            cprev = tin.shape[3] if pre == "s" else RUP[lvl - 1][1]
-            g_skip[7 - lvl].append(gcat[..., cprev:])
-            if pre == "s":
-                g = K.empty_nhwc(B, r // 2, r // 2, cprev, x)
-                K.upsample2x_bwd(gcat[..., :cprev], g, mask=below, slope=0.2)
-            else:
-                cin_up, cup = RUP[lvl - 1]
-                gr = K.empty_nhwc(B, r // 2, r // 2, 4 * cup, x)
-                K.pixel_shuffle2_bwd(gcat[..., :cup], gr)
-                gq = K.geom_fwd(B, r // 2, r // 2, 1, 1, 0)
-                wn = f"r_up{lvl}.upsample.0.weight"
-                if want(wn):
-                    src_u = cot(f"r_up{lvl}", gr)
-                    if src_u is not None:
-                        side.run(lambda src_u=src_u, tin=tin, gq=gq, wn=wn, cup=cup, cin_up=cin_up, lvl=lvl: K.wgrad(
-                            src_u(), tin, gq, 4 * cup, cin_up, sink.get(wn), cin_up, 1, db=sink.get(f"r_up{lvl}.upsample.0.bias"), accumulate=True), gr, tin)
-                g = K.empty_nhwc(B, r // 2, r // 2, cin_up, x)
-                K.conv(gr, P[wn], gq, cin_up, 4 * cup, 1, cin_up, g, mask=below, mask_slope=0.2)
-        in_decoder[0] = False
-        return g
-
-    def decoders_backward_both():
-        """decoder_backward for the restoration and the pixel-level decoder level by level, the data gradients of their mirror convs in
-        pairs (kernels.conv_pair).  Every launch and every append happens in the order of two decoder_backward calls, "r" first."""
-        in_decoder[0] = True
-        D2 = {"r": (g_rec, tp.r_cat, tp.r_o1, tp.r_o2, tp.r_in, "rec_out"), "s": (g_dec, tp.s_cat, tp.s_o1, tp.s_o2, tp.s_in, "dec_out")}
         g = {}
-        for pre in "rs":
-            g_out, _cats, _o1s, o2s, _ins, head = D2[pre]
-            t6 = o2s[6]
+        for pre in decs:
+            head, g_out = HEAD[pre], (g_dec if pre == "s" else g_rec)
+            t6 = tp.dec[pre][6][3]
             if want(head + ".weight"):
                 src_h = cot(head, g_out)
                 if src_h is not None:
-                    side.run(lambda src_h=src_h, t6=t6, head=head: K.wgrad(src_h(), t6, g64, 1, 1, sink.get(head + ".weight"), 1, 1,
-                                                                          db=sink.get(head + ".bias"), accumulate=True), g_out, t6)
+                    side.run(lambda: K.wgrad(src_h(), t6, g64, 1, 1, sink.get(head + ".weight"), 1, 1, db=sink.get(head + ".bias"), accumulate=True),
+                             g_out, t6)
+            # every cotangent that reaches a level's second conv is multiplied by that conv's LeakyReLU gradient; the producer of the
+            # cotangent (head conv, upsampling adjoint, 1x1 up-conv data gradient) applies it in its epilogue instead of a pass of its own
             g[pre] = K.empty_nhwc(B, 64, 64, 1, x)
-            K.conv(g_out, P[head + ".weight"], g64, 1, 1, 1, 1, g[pre], mask=o2s[6], mask_slope=0.2)
+            K.conv(g_out, P[head + ".weight"], g64, 1, 1, 1, 1, g[pre], mask=t6, mask_slope=0.2)
         for lvl in range(6, 0, -1):
             r = 2 ** lvl
             ccat, co = DEC[lvl - 1]
-            gpre1, gcat = {}, {}
-            for pre in "rs":
-                wgrad_sn(f"{pre}_dconv{lvl}2", g[pre], D2[pre][2][lvl], (r, 3, 1, 1), co, co, 3, yout=D2[pre][3][lvl])
-                gpre1[pre] = K.empty_nhwc(B, r, r, co, x)
-            K.conv_pair(*[dgrad_s1_call(f"{pre}_dconv{lvl}2", g[pre], r, co, co, gpre1[pre], mask=D2[pre][2][lvl]) for pre in "rs"])
-            for pre in "rs":
-                wgrad_sn(f"{pre}_dconv{lvl}1", gpre1[pre], D2[pre][1][lvl], (r, 3, 1, 1), co, ccat, 3, yout=D2[pre][2][lvl])
-                gcat[pre] = K.empty_nhwc(B, r, r, ccat, x)
-            K.conv_pair(*[dgrad_s1_call(f"{pre}_dconv{lvl}1", gpre1[pre], r, ccat, co, gcat[pre]) for pre in "rs"])
-            for pre in "rs":
-                _g_out, _cats, _o1s, o2s, ins, _head = D2[pre]
-                tin = ins[lvl]
-                below = o2s[lvl - 1] if lvl > 1 else None
+            for j, cin in ((2, co), (1, ccat)):          # the level's second conv, then its first: weight gradient, data gradient
+                calls, gin = [], {}
+                for pre in decs:
+                    _tin, cat, o1, o2 = tp.dec[pre][lvl]
+                    inp, outp = (o1, o2) if j == 2 else (cat, o1)
+                    wgrad_sn(f"{pre}_dconv{lvl}{j}", g[pre], inp, (r, 3, 1, 1), co, cin, 3, yout=outp)      # (g: already times outp > 0 ? 1 : 0.2)
+                    gin[pre] = K.empty_nhwc(B, r, r, cin, x)
+                    calls.append(dgrad_s1_call(f"{pre}_dconv{lvl}{j}", g[pre], r, cin, co, gin[pre], mask=o1 if j == 2 else None))
+                if len(calls) == 2:
+                    K.conv_pair(*calls)
+                else:
+                    yield calls[0]
+                g = gin
+            for pre in decs:                             # the way down: the skip's share, then the upsampling adjoint
+                gcat, tin = g[pre], tp.dec[pre][lvl][0]
+                below = tp.dec[pre][lvl - 1][3] if lvl > 1 else None      # output of the level below (None: the bottleneck, masked by the caller)
                 cprev = tin.shape[3] if pre == "s" else RUP[lvl - 1][1]
-                g_skip[7 - lvl].append(gcat[pre][..., cprev:])
+                g_skip[7 - lvl].append(gcat[..., cprev:])
                 if pre == "s":
                     g[pre] = K.empty_nhwc(B, r // 2, r // 2, cprev, x)
-                    K.upsample2x_bwd(gcat[pre][..., :cprev], g[pre], mask=below, slope=0.2)
+                    K.upsample2x_bwd(gcat[..., :cprev], g[pre], mask=below, slope=0.2)
                 else:
                     cin_up, cup = RUP[lvl - 1]
                     gr = K.empty_nhwc(B, r // 2, r // 2, 4 * cup, x)
-                    K.pixel_shuffle2_bwd(gcat[pre][..., :cup], gr)
+                    K.pixel_shuffle2_bwd(gcat[..., :cup], gr)
                     gq = K.geom_fwd(B, r // 2, r // 2, 1, 1, 0)
                     wn = f"r_up{lvl}.upsample.0.weight"
                     if want(wn):
                         src_u = cot(f"r_up{lvl}", gr)
                         if src_u is not None:
-                            side.run(lambda src_u=src_u, tin=tin, gq=gq, wn=wn, cup=cup, cin_up=cin_up, lvl=lvl: K.wgrad(
-                                src_u(), tin, gq, 4 * cup, cin_up, sink.get(wn), cin_up, 1, db=sink.get(f"r_up{lvl}.upsample.0.bias"), accumulate=True), gr, tin)
+                            side.run(lambda: K.wgrad(src_u(), tin, gq, 4 * cup, cin_up, sink.get(wn), cin_up, 1,
+                                                     db=sink.get(f"r_up{lvl}.upsample.0.bias"), accumulate=True), gr, tin)
                     g[pre] = K.empty_nhwc(B, r // 2, r // 2, cin_up, x)
                     K.conv(gr, P[wn], gq, cin_up, 4 * cup, 1, cin_up, g[pre], mask=below, mask_slope=0.2)
         in_decoder[0] = False
-        return g["r"], g["s"]
+        return [g[pre] for pre in decs]
 
-    if PAIR_DECODERS and g_rec is not None and g_dec is not None:
-        g_bot_parts.extend(decoders_backward_both())
-    else:
-        if g_rec is not None:
-            g_bot_parts.append((yield from decoder_backward("r", g_rec, tp.r_cat, tp.r_o1, tp.r_o2, tp.r_in, "rec_out")))
-        if g_dec is not None:
-            g_bot_parts.append((yield from decoder_backward("s", g_dec, tp.s_cat, tp.s_o1, tp.s_o2, tp.s_in, "dec_out")))
+    # g_bot_parts and every g_skip[l] take the restoration decoder's share first, then the pixel-level decoder's
+    decs = tuple(pre for pre, g_out in (("r", g_rec), ("s", g_dec)) if g_out is not None)
+    for group in ([decs] if PAIR_DECODERS and len(decs) == 2 else [(pre,) for pre in decs]):
+        g_bot_parts.extend((yield from decoders_backward(group)))
+    # ---- image-level head
     if g_enc is not None:
         if want("enc_out.weight"):
             side.run(lambda: K.wgrad(g_enc, tp.cm, g1, 1, 512, sink.get("enc_out.weight"), 512, 1, db=sink.get("enc_out.bias"), accumulate=True), g_enc)
@@ -874,7 +741,6 @@ def _disc_backward_gen(rt, P, tp, g_enc, g_dec, g_rec, sink, want_input_grad, de
                 calls.append(((g, wd, gp, co, co, 16, co * 16, gpre2),
                               dict(add1=add1, add2=add2, mask=xl, mask_slope=0.2, **_scales(tp, f"down{l}", gp))))
         K.conv_multi(calls)
-        g3 = K.geom_fwd(B, h, h, 3, 1, 1)
         wgrad_sn(f"conv{l}2", gpre2, a, (h, 3, 1, 1), co, co, 3, yout=xl)
         gpre1 = K.empty_nhwc(B, h, h, co, x)
         yield dgrad_s1_call(f"conv{l}2", gpre2, h, co, co, gpre1, mask=a)

@@ -405,9 +405,7 @@ def d_loss(method, x, y):
     # first, in the reference's order, and every conv applies the 1/sigma of the half it is computing (scale2 /
     # scale_split).  Same arithmetic per image; half the launches, twice the pixels per launch on the deep 4x4 .. 1x1 layers.
     DP.settle_tail(dev)                       # (a deep range still on the side stream: only if no G step followed the last D step)
-    K.prepack(DP.conv_views(P, True))
-    K.prepack_winograd(DP.winograd_views(P, True))
-    K.prepack_winograd_s2(DP.winograd_s2_views(P, True))
+    DP.prepack_views(P, True)
     sn = DP._sn_forward_multi(P, train, dev, 4)
     masks = D._next_masks(B, dev, 4)          # the four passes' dropout multipliers, stacked: (4B, 512) or None
     m12, m34 = (None, None) if masks is None else (masks[:2 * B], masks[2 * B:])
