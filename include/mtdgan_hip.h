@@ -583,6 +583,36 @@ size_t mtd_haarpsi_ws_bytes(int na, int B, int H, int W, int subsample);
 int mtd_haarpsi_each(const float* const a[3], int na, const float* b, int B, int H, int W, int subsample, float c, float alpha,
                      double* out, double* parts, void* ws, void* stream);
 
+/* ---- feature similarity index of the test loop (module/piq: fsim.py fsim, chromatic = False) -- DESIGN 3.17.
+ * Single-channel fp32 images (B, H, W) in [0, 1] (data_range 1), na in 1..3 sources srcs[k] against one target, image by image.
+ *   rescale by 255 and average-pool ks x ks (stride ks, floor) to the h x w = H / ks x W / ks map; the phase-congruency map from
+ *   the scales * orientations log-Gabor filters of `filters` (device, (orientations * scales, h, w) fp32, orientation-major, zero
+ *   frequency at [0, 0]) applied in the frequency domain: even / odd = real / imaginary part of ifft2(fft2(image) * filter), per
+ *   orientation the energy sum_s (even mean_e + odd mean_o - |even mean_o - odd mean_e|) less the noise threshold T_o, which
+ *   comes from the median (the element of rank (h w - 1) / 2) of the scale-0 squared amplitude and `consts` (device, 3 *
+ *   orientations doubles: em_n[o], sum_an2[o], sum_ai_aj[o]) and k; pc = (sum_o max(energy_o - T_o, 0) + eps) / (sum an + eps);
+ *   the Scharr gradient magnitude of the pooled map (zero padding 1); score = sum GM PC max(pc_a, pc_b) / sum max(pc_a, pc_b)
+ *   with the similarity constants 0.85 and 160.  eps is float32's; two all-zero images score exactly 1.
+ * out: (na, B) doubles.  parts (optional, may be null): (na, B, MTD_FSIM_SUMS + orientations) doubles: num, den, the sums of the
+ * source's phase-congruency and gradient maps, then the source's T_0 .. T_{O-1}.  fp32 transforms (radix-2 passes in LDS);
+ * everything from the filter responses on and every per-image sum in double in a fixed order: an image's numbers depend neither on
+ * the batch nor on its source slot.  A source whose pointer equals the target's shares the target's maps.  srcs is read on the
+ * host during the call (its first na entries).  ws: mtd_fsim_ws_bytes (of the POOLED sides); the batch is walked in chunks sized so
+ * that the workspace stays within 64 MiB, and the orientations in groups where one image of every set would not fit otherwise:
+ * at 256 x 256 pooled maps it is within 64 MiB for every allowed option and batch (DESIGN 3.17 has the rule).
+ * Null pointers, na outside 1..3, B < 1, ks < 1, a pooled side that is not a power of two in MTD_FSIM_MIN_SIDE .. MTD_FSIM_MAX_SIDE,
+ * scales outside 1..4, orientations outside 1..8, H * W > 2^30, a NaN k: MTD_EINVAL before any launch (the _ws_bytes query then
+ * returns 0).
+ * mtd_fsim_median: out[c] = the element of rank (n - 1) / 2 (torch.median's) of the n non-negative floats at values + c * n, by
+ * the radix select mtd_fsim_each's thresholds use. */
+#define MTD_FSIM_SUMS 4
+#define MTD_FSIM_MIN_SIDE 16
+#define MTD_FSIM_MAX_SIDE 512
+size_t mtd_fsim_ws_bytes(int na, int B, int h, int w, int scales, int orientations);
+int mtd_fsim_each(const void* const* srcs, int na, const void* target, int B, int H, int W, int ks, int scales, int orientations, float k,
+                  const float* filters, const double* consts, double* out, double* parts, void* ws, void* stream);
+int mtd_fsim_median(const float* values, int n, int count, float* out, void* stream);
+
 /* ---- perceptual metrics of the test loop (metrics.py:43-168: PL and TML on VGG-19 features; engine.py:139-140) ------
  * The convolutions of the feature stack are mtd_conv_* launches; these are the other pieces.  Maps are contiguous NHWC fp32,
  * 16-byte aligned (MTD_EALIGN).

@@ -286,6 +286,9 @@ def lib():
     sig("mtd_iqa_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, cf, vp, vp, vp, vp)
     sig("mtd_haarpsi_ws_bytes", sz, ci, ci, ci, ci, ci)
     sig("mtd_haarpsi_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, cf, cf, vp, vp, vp, vp)
+    sig("mtd_fsim_ws_bytes", sz, ci, ci, ci, ci, ci, ci)
+    sig("mtd_fsim_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, vp)
+    sig("mtd_fsim_median", ci, vp, ci, ci, vp, vp)
     sig("mtd_maxpool2x2", ci, vp, vp, ci, ci, ci, ci, vp)
     sig("mtd_patch_gram_l1_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_patch_gram_l1", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
@@ -383,6 +386,7 @@ EXPORTS = [
     "mtd_stored_to_hu", "mtd_stored_to_window", "mtd_window_to_stored",
     "mtd_iqa_ws_bytes", "mtd_iqa_each",
     "mtd_haarpsi_ws_bytes", "mtd_haarpsi_each",
+    "mtd_fsim_ws_bytes", "mtd_fsim_each", "mtd_fsim_median",
 ]
 
 

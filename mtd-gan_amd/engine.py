@@ -287,6 +287,33 @@ def _haarpsi_update(triple, meters):
     return (triple[2],)
 
 
+def _fsim_option(model):
+    """`model.test_fsim` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.fsim_each's defaults); a dict with keys
+    from scales, orientations, min_length, mult, sigma_f, delta_theta, k that metrics.fsim_check_options accepts -> those keyword
+    arguments.  Anything else: ValueError, before anything runs on the device."""
+    from . import metrics as M
+    cfg = getattr(model, "test_fsim", None)
+    if not cfg:
+        return None
+    if cfg is True:
+        return {}
+    try:
+        if not isinstance(cfg, dict) or set(cfg) - set(M.FSIM_OPTIONS):
+            raise ValueError("not a dict of the options")
+        M.fsim_check_options(**cfg)
+    except ValueError as e:
+        raise ValueError("model.test_fsim: True or a dict with the keys scales (1..4), orientations (1..8), min_length, mult, sigma_f, "
+                         f"delta_theta (positive numbers, sigma_f not 1), k (a number); got {cfg!r} ({e})") from None
+    return dict(cfg)
+
+
+def _fsim_update(triple, meters):
+    """The FSIM meters of one sample (after the sample's other keys); returns its CSV cell, the pred value."""
+    for who, v in zip(("input", "gt", "pred"), triple):
+        meters.setdefault(f"{who}_fsim", _Meter()).update(v, 1)
+    return (triple[2],)
+
+
 def _iqa_update(iqa, triples, meters):
     """The meters of one sample (after the sample's other keys); returns its CSV cells, the pred values."""
     for name, triple in zip(iqa, triples):
@@ -295,7 +322,7 @@ def _iqa_update(iqa, triples, meters):
     return tuple(t[2] for t in triples)
 
 
-def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa=None, haarpsi=None):
+def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa=None, haarpsi=None, fsim=None):
     """One loader batch of test_MTD_GAN_Ours under `model.test_per_slice`: B meter updates and B rows from one host read."""
     from . import kernels as K, metrics as M
     B, _, H, W = x.shape
@@ -310,6 +337,8 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
         parts.append(M.iqa_metrics_each(x, y, clipped, iqa).flatten())          # (metric, who, slice) float64, behind the others
     if haarpsi is not None:
         parts.append(M.haarpsi_each(x, y, clipped, **haarpsi).flatten())        # (who, slice) float64, behind the iqa block
+    if fsim is not None:
+        parts.append(M.fsim_each(x, y, clipped, **fsim).flatten())              # (who, slice) float64, behind the HaarPSI block
     vals = torch.cat(parts).tolist()                  # every per-slice value of the batch in one device -> host copy
     l1 = vals[:B]
     sums = [[vals[B + (k * B + i) * 2:B + (k * B + i) * 2 + 2] for i in range(B)] for k in range(3)]
@@ -317,6 +346,7 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
     pm = M._slice_triples(sums, H * W)
     q0 = (13 if vgg is not None else 7) * B           # where the iqa block starts
     q1 = q0 + 3 * B * len(iqa or ())                  # where the HaarPSI block starts
+    q2 = q1 + (3 * B if haarpsi is not None else 0)   # where the FSIM block starts
     paths = batch_data.get("path_n_20") if isinstance(batch_data, dict) else None
     for i in range(B):
         meters.setdefault("L1_loss", _Meter()).update(l1[i], 1)
@@ -332,6 +362,8 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
         more = _iqa_update(iqa, [tuple(vals[q0 + (r * 3 + k) * B + i] for k in range(3)) for r in range(len(iqa))], meters) if iqa is not None else ()
         if haarpsi is not None:
             more += _haarpsi_update(tuple(vals[q1 + k * B + i] for k in range(3)), meters)
+        if fsim is not None:
+            more += _fsim_update(tuple(vals[q2 + k * B + i] for k in range(3)), meters)
         path = paths[i] if paths is not None else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][i][2], pm["psnr"][i][2], pm["ssim"][i][2]) + more)
 
@@ -524,6 +556,14 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     the 3 B values travel in the batch's one device -> host copy, behind the IQA block.  Slices of at least 16 x 16 (ValueError
     otherwise).  Any other value of the attribute -- a dict with other keys, a non-positive c or alpha, a subsample that is not a
     bool -- is refused (ValueError) before anything runs; without it (or with a falsy value) nothing changes.
+    `model.test_fsim = True` (or a dict of scales, orientations, min_length, mult, sigma_f, delta_theta, k) adds the
+    reference's vendored piq metric FSIM (fsim with chromatic=False) of (input, gt, clipped prediction) against gt on the HIP
+    kernels of csrc/fsim.hip (metrics.fsim_each): the result gains input_fsim / gt_fsim / pred_fsim after the HaarPSI keys (before
+    the FID / KID keys) and the CSV the column FSIM after HaarPSI, holding the prediction's value.  On the default path a batch
+    gives one value per image set (the mean over its slices, one more host read); under `test_per_slice` the 3 B values travel
+    in the batch's one device -> host copy, behind the HaarPSI block.  The slices must pool (metrics.fsim_pooled_size) to sides
+    that are powers of two in 16..512 (ValueError otherwise).  Any other value of the attribute is refused (ValueError) before
+    anything runs; without it (or with a falsy value) nothing changes.
     `model.test_kid = True` (or a dict of metrics.kid_distance64's keyword arguments) adds piq's Kernel Inception
     Distance after the loop, from the same feature rows as FID and therefore only with `model.fid_features` (ValueError
     otherwise, before anything runs): the result gains input_kid / gt_kid / pred_kid behind the FID keys (metrics.compute_KID:
@@ -533,6 +573,7 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     falsy value) nothing changes."""
     _iqa_option(model)                                   # (a bad value is refused before anything else is set up)
     _haarpsi_option(model)
+    _fsim_option(model)
     _kid_option(model)
     stored = _StoredInput.from_model(model)
     dcm = _DcmSink.from_model(model, stored)
@@ -555,6 +596,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
     per_slice = bool(getattr(model, "test_per_slice", False))
     iqa = _iqa_option(model)
     haarpsi = _haarpsi_option(model)
+    fsim = _fsim_option(model)
     kid = _kid_option(model)
     feats = ([], [], [])
     meters = {}
@@ -579,7 +621,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         if dcm is not None:
             slices = dcm.begin(pred, words, table)             # likewise
         if per_slice:
-            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa, haarpsi)
+            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa, haarpsi, fsim)
             if png is not None:
                 png.submit(images, batch_data, k0)
             if dcm is not None:
@@ -607,6 +649,8 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
             more = _iqa_update(iqa, M.iqa_metrics_each(x, y, clipped, iqa).mean(dim=2).tolist(), meters)
         if haarpsi is not None:      # likewise
             more += _haarpsi_update(tuple(M.haarpsi_each(x, y, clipped, **haarpsi).mean(dim=1).tolist()), meters)
+        if fsim is not None:         # likewise
+            more += _fsim_update(tuple(M.fsim_each(x, y, clipped, **fsim).mean(dim=1).tolist()), meters)
         path = batch_data.get("path_n_20", [f"slice_{len(rows)}"])[0] if isinstance(batch_data, dict) else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]) + more)
         if png is not None:
@@ -618,7 +662,8 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         os.makedirs(save_dir, exist_ok=True)
         with open(os.path.join(save_dir, "pred_results.csv"), "w") as f:
             f.write((",PATH,PL,TML,RMSE,PSNR,SSIM" if vgg is not None else ",PATH,RMSE,PSNR,SSIM")
-                    + "".join("," + _IQA_COLUMNS[n] for n in iqa or ()) + (",HaarPSI" if haarpsi is not None else "") + "\n")
+                    + "".join("," + _IQA_COLUMNS[n] for n in iqa or ()) + (",HaarPSI" if haarpsi is not None else "") + (",FSIM" if fsim is not None else "")
+                    + "\n")
             for i, r in enumerate(rows):
                 f.write(f"{i}," + ",".join(str(v) for v in r) + "\n")
     if fid_features is not None:

@@ -29,7 +29,15 @@ kernels of csrc/kid.hip (`mtd_kid`): kid_distance64 / compute_KID (
 
 HaarPSI (module/piq/haarpsi.py: haarpsi with scales=3), the Haar wavelet perceptual similarity index, image by image on the HIP
 kernels of csrc/haarpsi.hip (`mtd_haarpsi_each`): haarpsi_each / haarpsi_per_slice and compute_HaarPSI
-(engine.test_MTD_GAN_Ours under `model.test_haarpsi`)."""
+(engine.test_MTD_GAN_Ours under `model.test_haarpsi`).
+
+FSIM (module/piq/fsim.py: fsim with chromatic=False), the feature similarity index from phase congruency and gradient magnitude,
+image by image on the HIP kernels of csrc/fsim.hip (`mtd_fsim_each`): fsim_each / fsim_per_slice and compute_FSIM
+(engine.test_MTD_GAN_Ours under `model.test_fsim`).  The log-Gabor filter table and its three noise constants are built on the
+host once per (pooled size, options) and uploaded once per device (fsim_filter_table / fsim_constants)."""
+import functools
+import math
+
 import numpy as np
 import torch
 
@@ -272,6 +280,143 @@ def compute_HaarPSI(input, target, pred, data_range=1.0, **kw):
     if data_range != 1.0:
         raise NotImplementedError("haarpsi: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
     return tuple(haarpsi_each(input, target, pred, **kw).mean(dim=1).tolist())
+
+
+# ================================================================================================ FSIM
+FSIM_MIN_SIDE, FSIM_MAX_SIDE = 16, 512                          # of the pooled map; each side a power of two (the LDS transforms' lengths)
+FSIM_SUMS = 4                                                   # num, den, sum pc, sum gm; the parts rows hold the T_o behind them
+FSIM_OPTIONS = ("scales", "orientations", "min_length", "mult", "sigma_f", "delta_theta", "k")
+
+
+def fsim_pooled_size(H, W):
+    """-> (ks, h, w): piq's average-pool kernel max(1, round(min(H, W) / 256)) -- Python's round, to even: 384 -> 2, 640 -> 2 --
+    and the sides of the pooled map (stride ks, floor)."""
+    ks = max(1, round(min(H, W) / 256))
+    return ks, H // ks, W // ks
+
+
+def fsim_check_options(scales=4, orientations=4, min_length=6, mult=2, sigma_f=0.55, delta_theta=1.2, k=2.0):
+    """ValueError unless scales is an int in 1..4, orientations an int in 1..8, min_length, mult and delta_theta positive
+    numbers, sigma_f a positive number other than 1 and k a finite number."""
+    integer = lambda v, lo, hi: isinstance(v, int) and not isinstance(v, bool) and lo <= v <= hi          # noqa: E731
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)      # noqa: E731
+    if not integer(scales, 1, 4) or not integer(orientations, 1, 8):
+        raise ValueError(f"fsim: scales an int in 1..4 and orientations an int in 1..8, got {scales!r}, {orientations!r}")
+    if not all(number(v) and v > 0 for v in (min_length, mult, sigma_f, delta_theta)) or sigma_f == 1 or not number(k):
+        raise ValueError("fsim: min_length, mult, delta_theta positive numbers, sigma_f a positive number other than 1, k a number; got "
+                         f"{min_length!r}, {mult!r}, {delta_theta!r}, {sigma_f!r}, {k!r}")
+
+
+def _fsim_frequencies(n):
+    """The n frequencies of a transform axis in storage order (0, 1/n, ..., then the negative ones), float32."""
+    k = (torch.arange(n) + n // 2) % n - n // 2
+    return k.float() / n
+
+
+@functools.lru_cache(maxsize=16)
+def fsim_filter_table(h, w, scales=4, orientations=4, min_length=6, mult=2, sigma_f=0.55, delta_theta=1.2):
+    """The (orientations * scales, h, w) float32 host table of piq's log-Gabor filters for even h, w, orientation-major, zero
+    frequency at [0, 0]: a radial factor per scale (log-Gabor profile times a Butterworth low-pass of cutoff 0.45 and order 15,
+    zero at the zero frequency) times an angular Gaussian per orientation, both built for all scales / orientations at once from
+    broadcast frequency axes.  float32 throughout, as piq's grid is even in a float64 run, and each element through piq's
+    sequence of roundings, so the bytes are those of piq's own table (tests/golden/fsim_piq.npz holds their CRC-32).  Cached; do
+    not modify the result."""
+    fy, fx = _fsim_frequencies(h)[:, None], _fsim_frequencies(w)[None, :]
+    radius = torch.sqrt(fy * fy + fx * fx)                                          # (h, w)
+    butterworth = 1.0 / (1.0 + (radius / 0.45) ** 30)
+    direction = torch.atan2(-fx, fy).expand(h, w)
+    radius[0, 0] = 1                                                                # log(0) stays out; the factor is zeroed below
+    centres = torch.tensor([1.0 / (min_length * mult ** s) for s in range(scales)])[:, None, None]
+    radial = torch.exp(-torch.log(radius / centres) ** 2 / (2 * math.log(sigma_f) ** 2)) * butterworth          # (S, h, w)
+    radial[:, 0, 0] = 0
+    angles = [o * math.pi / orientations for o in range(orientations)]
+    ca, sa = (torch.tensor([f(a) for a in angles])[:, None, None] for f in (math.cos, math.sin))
+    sd, cd = torch.sin(direction), torch.cos(direction)
+    away = torch.atan2(sd * ca - cd * sa, cd * ca + sd * sa).abs()                  # (O, h, w): angle to the orientation, unwrapped
+    width = math.pi / (orientations * delta_theta)
+    angular = torch.exp(-away ** 2 / (2 * width ** 2))
+    return (angular[:, None] * radial[None]).reshape(orientations * scales, h, w).contiguous()
+
+
+def fsim_constants(table, scales, orientations):
+    """The (3, orientations) float64 constants of the noise threshold from the float32 table: em_n[o] = sum filter[o, 0]^2, and
+    from the Gram matrix over the scales of f = real(ifft2(filter)) sqrt(h w): sum_an2[o] its trace, sum_ai_aj[o] the sum of its
+    upper triangle."""
+    h, w = table.shape[-2:]
+    t = table.double().view(orientations, scales, h, w)
+    f = torch.fft.ifft2(t).real * math.sqrt(h * w)
+    gram = torch.einsum("osyx,otyx->ost", f, f)
+    trace = gram.diagonal(dim1=1, dim2=2).sum(dim=1)
+    return torch.stack([(t[:, 0] ** 2).sum(dim=[1, 2]), trace, (gram.sum(dim=[1, 2]) - trace) / 2]).contiguous()
+
+
+_fsim_device_tables = {}
+
+
+def _fsim_tables(h, w, scales, orientations, min_length, mult, sigma_f, delta_theta, device):
+    key = (h, w, scales, orientations, min_length, mult, sigma_f, delta_theta, device.index if device.index is not None else torch.cuda.current_device())
+    got = _fsim_device_tables.get(key)
+    if got is None:
+        table = fsim_filter_table(h, w, scales, orientations, min_length, mult, sigma_f, delta_theta)
+        got = (table.to(device), fsim_constants(table, scales, orientations).to(device))
+        if len(_fsim_device_tables) >= 16:
+            _fsim_device_tables.clear()
+        _fsim_device_tables[key] = got
+    return got
+
+
+def fsim_each(input, target, pred, scales=4, orientations=4, min_length=6, mult=2, sigma_f=0.55, delta_theta=1.2, k=2.0, parts=False):
+    """FSIM (piq's fsim with chromatic=False, data_range 1) of every slice of (input, target, pred) against the same slice of
+    target, without a host read: a (3, B) float64 device tensor.  With parts=True also the (3, B, 4 + orientations) float64 rows
+    num = sum GM PC pc_max, den = sum pc_max, the sums of the source's phase-congruency and gradient maps, and its noise thresholds
+    T_0 .. T_{O-1}.  A slice's values depend neither on the batch it is in nor on the other two image sets (mtd_fsim_each: fp32
+    LDS transforms, everything after them in double in a fixed order); an image set passed twice (target as a source) is
+    transformed once.  Two all-zero images give exactly 1, as piq does.  The pooled map (fsim_pooled_size) must have sides that
+    are powers of two in 16..512: 64 x 64 patches, 256 x 256, 512 x 512 and 1024 x 1024 slices, 512 x 256 ...; anything else is a
+    ValueError that names the pooled size."""
+    for t in (input, target, pred):
+        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
+            raise AssertionError("fsim expects (B,1,H,W) tensors of the same shape")
+    fsim_check_options(scales, orientations, min_length, mult, sigma_f, delta_theta, k)
+    B, _, H, W = target.shape
+    ks, h, w = fsim_pooled_size(H, W)
+    if not all(FSIM_MIN_SIDE <= n <= FSIM_MAX_SIDE and n & (n - 1) == 0 for n in (h, w)):
+        raise ValueError(f"fsim: {H}x{W} images pool (kernel {ks}) to {h}x{w}; the kernels take pooled sides that are powers of two in "
+                         f"{FSIM_MIN_SIDE}..{FSIM_MAX_SIDE}")
+    for t in (input, target, pred):
+        if not t.is_cuda:
+            raise RuntimeError("fsim: HIP path needs CUDA tensors (no CPU fallback)")
+    import ctypes
+    srcs, kept = [], {}
+    for t in (input, target, pred):                              # (the same tensor twice stays the same pointer: transformed once)
+        if id(t) not in kept:
+            kept[id(t)] = t.contiguous().float()
+        srcs.append(kept[id(t)])
+    L = _lib.lib()
+    dev = srcs[1].device
+    table, consts = _fsim_tables(h, w, scales, orientations, min_length, mult, sigma_f, delta_theta, dev)
+    out = torch.empty((3, B), dtype=torch.float64, device=dev)
+    rows = torch.empty((3, B, FSIM_SUMS + orientations), dtype=torch.float64, device=dev) if parts else None
+    ws = K.workspace(L.mtd_fsim_ws_bytes(3, B, h, w, scales, orientations), dev)
+    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    _lib.check(L.mtd_fsim_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, ks, scales, orientations, float(k), table.data_ptr(), consts.data_ptr(),
+                               out.data_ptr(), rows.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_fsim_each")
+    return (out, rows) if parts else out
+
+
+def fsim_per_slice(input, target, pred, **kw):
+    """fsim_each as host numbers: a list of B (input, gt, pred) triples (the kernels' float64 scores).  One device -> host copy
+    for the batch."""
+    vals = fsim_each(input, target, pred, **kw).tolist()
+    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+
+
+def compute_FSIM(input, target, pred, data_range=1.0, **kw):
+    """piq's fsim(a, target, chromatic=False) with its defaults (or the seven options) for a = input, target, pred: (input, gt,
+    pred) floats, each the mean over the batch of the per-image scores (reduction='mean')."""
+    if data_range != 1.0:
+        raise NotImplementedError("fsim: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
+    return tuple(fsim_each(input, target, pred, **kw).mean(dim=1).tolist())
 
 
 # ================================================================================================ perceptual metrics
