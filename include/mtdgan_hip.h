@@ -645,6 +645,72 @@ int mtd_patch_gram_l1_each(const float* X, const float* Y, int B, int h, int w, 
                            void* stream);
 int mtd_scaled_sums_f64(const double* in, int groups, int per, const double* scales_host, float* out, void* stream);
 
+/* ---- LPIPS and DISTS of the test loop (module/piq/perceptual.py: LPIPS, DISTS on VGG-16 features) -- DESIGN 3.18 ----------
+ * The convolutions of the feature stack are mtd_conv_* launches and its max-pools mtd_maxpool2x2; these are the other pieces.
+ * Maps are contiguous NHWC fp32, 16-byte aligned where C is a multiple of 4 (MTD_EALIGN).  No atomics; every per-image number is
+ * a double formed in a fixed order in two stages (workgroup partials in ws, then a finish), and image i of a batch has the bits
+ * of the one-image call on image i.  Null pointers and shapes outside the rules: MTD_EINVAL before any launch (a _ws_bytes
+ * query then returns 0).
+ *   mtd_l2pool3x3s2       DISTS's L2Pool2d(3, stride 2, padding 1): out (B, ceil(H/2), ceil(W/2), C) from in (B, H, W, C),
+ *                         out = sqrt(sum over the 3 x 3 window of k x^2 + 1e-12), k = [[1,2,1],[2,4,2],[1,2,1]] / 16, zeros outside
+ *                         the map; the taps are added row-major in fp32 (fmaf(k, x * x, acc)).  Any B, H, W >= 1, C a multiple
+ *                         of 4.  One float4 of channels per thread and round; at most MTD_L2POOL_MAX_BLOCKS workgroups of 256
+ *                         threads, so maps of more than 256 * MTD_L2POOL_MAX_BLOCKS output float4 take further rounds.
+ *   mtd_lpips_level_each  t, a and b (b may be null) of shape (B, h, w, C), C in {64, 128, 256, 512}, h * w < 2^30, B <= 65535;
+ *                         weights: C device doubles.  For o = a (k = 0) and o = b (k = 1, when given):
+ *                           out[k * other_stride + i * out_stride] = sum over the pixels of image i and c of w_c d(o_c / (|o| + 1e-10), t_c / (|t| + 1e-10)),
+ *                         |.| the 2-norm over a pixel's channels, d(x, y) = (x - y)^2 (MTD_LPIPS_MSE) or |x - y| (MTD_LPIPS_MAE);
+ *                         the spatial mean is this over h * w.  Floats are converted on load and everything is double: a pixel's
+ *                         norms are sums over its C channels (a lane's 4 or 8 in sequence, then a butterfly over the
+ *                         LP = min(C / 4, 64) lanes of the pixel), 1 / (|.| + 1e-10) is one division per pixel and map.  o == t
+ *                         (the same values) gives exactly 0; an all-zero pixel contributes 0.  Launch arithmetic: a workgroup
+ *                         of 256 threads takes P = 4 * 64 / LP pixels per round, an image gets
+ *                         nblk = min(ceil(h w / P), MTD_LPIPS_MAX_BLOCKS) workgroups and so R = ceil(h w / (P nblk)) rounds.  A
+ *                         lane adds its C / LP terms of R pixels in sequence, then 6 butterfly steps, the 4 waves in 2 steps,
+ *                         the finish ceil(nblk / 256) partials per thread and an 8-step tree: no number passes through more than
+ *                         (C / LP) R + 6 + 2 + ceil(nblk / 256) + 8 additions (the summation depth).  ws:
+ *                         mtd_lpips_level_ws_bytes(B, h, w, C).  out_stride < 1 or another distance flag: MTD_EINVAL.
+ *   mtd_scaled_sums_f64_f64  mtd_scaled_sums_f64 with a double result: out[g] = sum_i scales_host[i] * in[g * per + i], added in
+ *                         the order of i; parts (optional, may be null) gets the groups * per scaled terms.
+ *   mtd_channel_moments_each  t, a and b (b may be null) of shape (B, h, w, C), C = 1 or a multiple of 4 up to 1024,
+ *                         h * w < 2^30, B <= 65535.  out: (B, C, K) doubles, K = 2 + 3 n_others, per image and channel
+ *                         (sum t, sum t^2) and then per other map (sum o, sum o^2, sum o t) over the pixels.  A product of two
+ *                         floats is exact in double, so only the additions round.  Launch arithmetic: a thread owns a float4 of
+ *                         channels (the one channel when C = 1), PL = 256 / (C / 4) (256 when C = 1) threads share a channel group
+ *                         and walk a pixel range with stride PL; an image is cut into
+ *                         ranges = min(ceil(h w / (PL * MTD_MOMENTS_WALK)), MTD_MOMENTS_MAX_RANGES) ranges of
+ *                         ceil(h w / ranges) pixels.  A thread adds ceil(range / PL) terms in sequence, the PL threads meet in
+ *                         a halving tree (ceil(log2 PL) steps) and the finish adds the ranges in index order: the summation
+ *                         depth is ceil(range / PL) + ceil(log2 PL) + ranges.  ws: mtd_channel_moments_ws_bytes.
+ *   mtd_dists_finish      tables[l], l < MTD_DISTS_LEVELS = 6: the moment tables of the raw image (C = 1) and the five VGG-16
+ *                         maps (C = 64, 128, 256, 512, 512), all of one n_others and B; pixels[l]: h * w of level l; alpha, beta:
+ *                         1475 = 3 + 64 + 128 + 256 + 512 + 512 device doubles each, whose first three all weigh the grey channel.
+ *                         With mu = sum / n, var = sum of squares / n - mu^2, cov = sum o t / n - mu_o mu_t:
+ *                           S1 = (2 mu_o mu_t + 1e-6) / (mu_o^2 + mu_t^2 + 1e-6), S2 = (2 cov + 1e-6) / (var_o + var_t + 1e-6),
+ *                           out[r * B + i] = 1 - sum over levels (sum over channels of alpha S1 + beta S2),
+ *                         a level's channels by a 256-thread fixed-order sum, the levels in order.  Rows r: the others in
+ *                         order; with self_row in 0 .. n_others one more row is inserted at that index for the target against
+ *                         itself, whose S1 and S2 are exactly 1 in this arithmetic (no table is read for it): n_others +
+ *                         (self_row >= 0) rows.  parts (optional, may be null): (rows, B, 6) doubles, the level sums.  tables
+ *                         and pixels are read on the host during the call. */
+#define MTD_L2POOL_MAX_BLOCKS 2048
+#define MTD_LPIPS_MAX_BLOCKS 1024
+#define MTD_LPIPS_MSE 0
+#define MTD_LPIPS_MAE 1
+#define MTD_MOMENTS_MAX_RANGES 256
+#define MTD_MOMENTS_WALK 32
+#define MTD_DISTS_LEVELS 6
+#define MTD_DISTS_WEIGHTS 1475
+int mtd_l2pool3x3s2(const float* in, float* out, int B, int H, int W, int C, void* stream);
+size_t mtd_lpips_level_ws_bytes(int B, int h, int w, int C);
+int mtd_lpips_level_each(const float* t, const float* a, const float* b, int B, int h, int w, int C, const double* weights, int distance,
+                         double* out, long long out_stride, long long other_stride, void* ws, void* stream);
+int mtd_scaled_sums_f64_f64(const double* in, int groups, int per, const double* scales_host, double* out, double* parts, void* stream);
+size_t mtd_channel_moments_ws_bytes(int B, int h, int w, int C, int n_others);
+int mtd_channel_moments_each(const float* t, const float* a, const float* b, int B, int h, int w, int C, double* out, void* ws, void* stream);
+int mtd_dists_finish(const double* const tables[MTD_DISTS_LEVELS], const long long pixels[MTD_DISTS_LEVELS], int n_others, int B, int self_row,
+                     const double* alpha, const double* beta, double* out, double* parts, void* stream);
+
 /* ---- Frechet distance of the test loop (module/piq/fid.py; metrics.py:33-41, engine.py:179-181) -- DESIGN 3.8 -----------
  * The statistic only: the feature network stays the caller's.  float64 throughout, products on v_mfma_f64_16x16x4_f64.  All
  * matrices are contiguous row-major, D x D doubles, 1 <= D <= 16384, 8-byte aligned; no size is special (edge tiles and the

@@ -293,6 +293,13 @@ def lib():
     sig("mtd_patch_gram_l1_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_patch_gram_l1", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
     sig("mtd_scaled_sums_f64", ci, vp, ci, ci, C.POINTER(C.c_double), vp, vp)
+    sig("mtd_l2pool3x3s2", ci, vp, vp, ci, ci, ci, ci, vp)
+    sig("mtd_lpips_level_ws_bytes", sz, ci, ci, ci, ci)
+    sig("mtd_lpips_level_each", ci, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ll, ll, vp, vp)
+    sig("mtd_scaled_sums_f64_f64", ci, vp, ci, ci, C.POINTER(C.c_double), vp, vp, vp)
+    sig("mtd_channel_moments_ws_bytes", sz, ci, ci, ci, ci, ci)
+    sig("mtd_channel_moments_each", ci, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp)
+    sig("mtd_dists_finish", ci, C.POINTER(vp), C.POINTER(C.c_longlong), ci, ci, ci, vp, vp, vp, vp, vp)
     cd = C.c_double
     sig("mtd_fid_ws_bytes", sz, ci)
     sig("mtd_fid_stats", ci, vp, ci, ci, vp, vp, vp, vp)
@@ -387,6 +394,8 @@ EXPORTS = [
     "mtd_iqa_ws_bytes", "mtd_iqa_each",
     "mtd_haarpsi_ws_bytes", "mtd_haarpsi_each",
     "mtd_fsim_ws_bytes", "mtd_fsim_each", "mtd_fsim_median",
+    "mtd_l2pool3x3s2", "mtd_lpips_level_ws_bytes", "mtd_lpips_level_each", "mtd_scaled_sums_f64_f64",
+    "mtd_channel_moments_ws_bytes", "mtd_channel_moments_each", "mtd_dists_finish",
 ]
 
 

@@ -314,6 +314,61 @@ def _fsim_update(triple, meters):
     return (triple[2],)
 
 
+def _lpips_option(model):
+    """`model.test_lpips` of test_MTD_GAN_Ours: absent or falsy -> None; LPIPS's linear-layer weights in a form
+    metrics.lpips_weights takes (five tensors, or a path), or `dict(weights=..., distance="mse" | "mae")` -> the keyword arguments
+    of metrics.lpips_each (vgg, weights as the float64 table, distance).  It needs `model.perceptual_vgg16`, a
+    metrics.VGG16Features.  Anything else: ValueError, before anything runs on the device."""
+    from . import metrics as M
+    cfg = getattr(model, "test_lpips", None)
+    if cfg is None or cfg is False or (isinstance(cfg, (dict, list, tuple, str)) and not cfg):
+        return None
+    distance = "mse"
+    if isinstance(cfg, dict):
+        if set(cfg) - {"weights", "distance"} or "weights" not in cfg:
+            raise ValueError(f"model.test_lpips: the weights, or a dict with the keys weights and distance; got the keys {sorted(cfg)}")
+        cfg, distance = cfg["weights"], cfg.get("distance", "mse")
+    if distance not in M.LPIPS_DISTANCES:
+        raise ValueError(f"model.test_lpips: distance must be one of {M.LPIPS_DISTANCES}, got {distance!r}")
+    if cfg is True:
+        raise ValueError("model.test_lpips: no weights ship with this package; pass LPIPS's five linear-layer weight tensors or a path to them")
+    try:
+        table = M.lpips_weights(cfg)
+    except (ValueError, OSError) as e:
+        raise ValueError(f"model.test_lpips: {e}") from None
+    vgg = getattr(model, "perceptual_vgg16", None)
+    if not isinstance(vgg, M.VGG16Features):
+        raise ValueError("model.test_lpips needs model.perceptual_vgg16 = metrics.VGG16Features(state_dict): LPIPS is computed on its maps")
+    return dict(vgg=vgg, weights=table, distance=distance)
+
+
+def _dists_option(model):
+    """`model.test_dists` of test_MTD_GAN_Ours: absent or falsy -> None; DISTS's alpha / beta in a form metrics.dists_weights takes
+    (a dict with `alpha` and `beta`, or a path) -> the keyword arguments of metrics.dists_each (vgg, weights as the float64
+    table).  It needs `model.perceptual_vgg16`.  Anything else: ValueError, before anything runs on the device."""
+    from . import metrics as M
+    cfg = getattr(model, "test_dists", None)
+    if cfg is None or cfg is False or (isinstance(cfg, (dict, list, tuple, str)) and not cfg):
+        return None
+    if cfg is True:
+        raise ValueError("model.test_dists: no weights ship with this package; pass DISTS's dict of alpha and beta or a path to it")
+    try:
+        table = M.dists_weights(cfg)
+    except (ValueError, OSError) as e:
+        raise ValueError(f"model.test_dists: {e}") from None
+    vgg = getattr(model, "perceptual_vgg16", None)
+    if not isinstance(vgg, M.VGG16Features):
+        raise ValueError("model.test_dists needs model.perceptual_vgg16 = metrics.VGG16Features(state_dict): DISTS is computed on its maps")
+    return dict(vgg=vgg, weights=table)
+
+
+def _named_update(name, triple, meters):
+    """The {input,gt,pred}_<name> meters of one sample (after the sample's other keys); returns its CSV cell, the pred value."""
+    for who, v in zip(("input", "gt", "pred"), triple):
+        meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+    return (triple[2],)
+
+
 def _iqa_update(iqa, triples, meters):
     """The meters of one sample (after the sample's other keys); returns its CSV cells, the pred values."""
     for name, triple in zip(iqa, triples):
@@ -322,7 +377,8 @@ def _iqa_update(iqa, triples, meters):
     return tuple(t[2] for t in triples)
 
 
-def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa=None, haarpsi=None, fsim=None):
+def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa=None, haarpsi=None, fsim=None, lpips=None,
+                          dists=None):
     """One loader batch of test_MTD_GAN_Ours under `model.test_per_slice`: B meter updates and B rows from one host read."""
     from . import kernels as K, metrics as M
     B, _, H, W = x.shape
@@ -339,6 +395,10 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
         parts.append(M.haarpsi_each(x, y, clipped, **haarpsi).flatten())        # (who, slice) float64, behind the iqa block
     if fsim is not None:
         parts.append(M.fsim_each(x, y, clipped, **fsim).flatten())              # (who, slice) float64, behind the HaarPSI block
+    if lpips is not None:
+        parts.append(M.lpips_each(x, y, clipped, **lpips).flatten())            # (who, slice) float64, behind the FSIM block
+    if dists is not None:
+        parts.append(M.dists_each(x, y, clipped, **dists).flatten())            # (who, slice) float64, behind the LPIPS block
     vals = torch.cat(parts).tolist()                  # every per-slice value of the batch in one device -> host copy
     l1 = vals[:B]
     sums = [[vals[B + (k * B + i) * 2:B + (k * B + i) * 2 + 2] for i in range(B)] for k in range(3)]
@@ -347,6 +407,8 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
     q0 = (13 if vgg is not None else 7) * B           # where the iqa block starts
     q1 = q0 + 3 * B * len(iqa or ())                  # where the HaarPSI block starts
     q2 = q1 + (3 * B if haarpsi is not None else 0)   # where the FSIM block starts
+    q3 = q2 + (3 * B if fsim is not None else 0)      # where the LPIPS block starts
+    q4 = q3 + (3 * B if lpips is not None else 0)     # where the DISTS block starts
     paths = batch_data.get("path_n_20") if isinstance(batch_data, dict) else None
     for i in range(B):
         meters.setdefault("L1_loss", _Meter()).update(l1[i], 1)
@@ -364,6 +426,10 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
             more += _haarpsi_update(tuple(vals[q1 + k * B + i] for k in range(3)), meters)
         if fsim is not None:
             more += _fsim_update(tuple(vals[q2 + k * B + i] for k in range(3)), meters)
+        if lpips is not None:
+            more += _named_update("lpips", tuple(vals[q3 + k * B + i] for k in range(3)), meters)
+        if dists is not None:
+            more += _named_update("dists", tuple(vals[q4 + k * B + i] for k in range(3)), meters)
         path = paths[i] if paths is not None else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][i][2], pm["psnr"][i][2], pm["ssim"][i][2]) + more)
 
@@ -564,6 +630,17 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     in the batch's one device -> host copy, behind the HaarPSI block.  The slices must pool (metrics.fsim_pooled_size) to sides
     that are powers of two in 16..512 (ValueError otherwise).  Any other value of the attribute is refused (ValueError) before
     anything runs; without it (or with a falsy value) nothing changes.
+    `model.test_lpips = <weights>` (LPIPS's five linear-layer weight tensors or a path to them, or `dict(weights=...,
+    distance="mse" | "mae")`) and `model.test_dists = <weights>` (DISTS's dict of alpha and beta, or a path) add the
+    reference's vendored piq metrics LPIPS and DISTS of (input, gt, clipped prediction) against gt on the feature network
+    `model.perceptual_vgg16 = metrics.VGG16Features(state_dict)` (the torchvision `vgg16` checkpoint and both weight files are the
+    caller's to hand over, none ships with this package) and the HIP kernels of csrc/lpips.hip (metrics.lpips_each /
+    dists_each): the result gains {input,gt,pred}_lpips and {input,gt,pred}_dists after the FSIM keys (before the FID / KID keys)
+    and the CSV the columns LPIPS and DISTS after FSIM, holding the prediction's values.  On the default path a batch gives one
+    value per image set (the mean over its slices, one more host read each); under `test_per_slice` the 3 B values of each travel
+    in the batch's one device -> host copy, behind the FSIM block.  Slices of at least 16 x 16.  Weights in another form, another
+    distance, or either option without `perceptual_vgg16` are refused (ValueError) before anything runs; without the attributes
+    (or with None / False) nothing changes.
     `model.test_kid = True` (or a dict of metrics.kid_distance64's keyword arguments) adds piq's Kernel Inception
     Distance after the loop, from the same feature rows as FID and therefore only with `model.fid_features` (ValueError
     otherwise, before anything runs): the result gains input_kid / gt_kid / pred_kid behind the FID keys (metrics.compute_KID:
@@ -574,6 +651,8 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     _iqa_option(model)                                   # (a bad value is refused before anything else is set up)
     _haarpsi_option(model)
     _fsim_option(model)
+    _lpips_option(model)
+    _dists_option(model)
     _kid_option(model)
     stored = _StoredInput.from_model(model)
     dcm = _DcmSink.from_model(model, stored)
@@ -597,6 +676,11 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
     iqa = _iqa_option(model)
     haarpsi = _haarpsi_option(model)
     fsim = _fsim_option(model)
+    lpips = _lpips_option(model)
+    dists = _dists_option(model)
+    for opt in (lpips, dists):                           # the small weight tables go to the device once, not once per batch
+        if opt is not None:
+            opt["weights"] = opt["weights"].to(device)
     kid = _kid_option(model)
     feats = ([], [], [])
     meters = {}
@@ -621,7 +705,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         if dcm is not None:
             slices = dcm.begin(pred, words, table)             # likewise
         if per_slice:
-            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa, haarpsi, fsim)
+            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa, haarpsi, fsim, lpips, dists)
             if png is not None:
                 png.submit(images, batch_data, k0)
             if dcm is not None:
@@ -651,6 +735,10 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
             more += _haarpsi_update(tuple(M.haarpsi_each(x, y, clipped, **haarpsi).mean(dim=1).tolist()), meters)
         if fsim is not None:         # likewise
             more += _fsim_update(tuple(M.fsim_each(x, y, clipped, **fsim).mean(dim=1).tolist()), meters)
+        if lpips is not None:        # likewise
+            more += _named_update("lpips", tuple(M.lpips_each(x, y, clipped, **lpips).mean(dim=1).tolist()), meters)
+        if dists is not None:        # likewise
+            more += _named_update("dists", tuple(M.dists_each(x, y, clipped, **dists).mean(dim=1).tolist()), meters)
         path = batch_data.get("path_n_20", [f"slice_{len(rows)}"])[0] if isinstance(batch_data, dict) else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]) + more)
         if png is not None:
@@ -663,7 +751,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         with open(os.path.join(save_dir, "pred_results.csv"), "w") as f:
             f.write((",PATH,PL,TML,RMSE,PSNR,SSIM" if vgg is not None else ",PATH,RMSE,PSNR,SSIM")
                     + "".join("," + _IQA_COLUMNS[n] for n in iqa or ()) + (",HaarPSI" if haarpsi is not None else "") + (",FSIM" if fsim is not None else "")
-                    + "\n")
+                    + (",LPIPS" if lpips is not None else "") + (",DISTS" if dists is not None else "") + "\n")
             for i, r in enumerate(rows):
                 f.write(f"{i}," + ",".join(str(v) for v in r) + "\n")
     if fid_features is not None:

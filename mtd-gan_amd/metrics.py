@@ -34,7 +34,15 @@ kernels of csrc/haarpsi.hip (`mtd_haarpsi_each`): haarpsi_each / ha
 FSIM (module/piq/fsim.py: fsim with chromatic=False), the feature similarity index from phase congruency and gradient magnitude,
 image by image on the HIP kernels of csrc/fsim.hip (`mtd_fsim_each`): fsim_each / fsim_per_slice and compute_FSIM
 (engine.test_MTD_GAN_Ours under `model.test_fsim`).  The log-Gabor filter table and its three noise constants are built on the
-host once per (pooled size, options) and uploaded once per device (fsim_filter_table / fsim_constants)."""
+host once per (pooled size, options) and uploaded once per device (fsim_filter_table / fsim_constants).
+
+LPIPS and DISTS (module/piq/perceptual.py: LPIPS and DISTS on torchvision's VGG-16 with ImageNet normalisation) image by image
+(DESIGN 3.18): the feature stack is `VGG16Features`, built like `VGG19Features` from a state dict the caller hands over, with the
+normalisation folded exactly into its first layer and max or L2 pooling (`mtd_l2pool3x3s2`); the reductions over the maps run on
+the HIP kernels of csrc/lpips.hip (`mtd_lpips_level_each`, `mtd_channel_moments_each`, `mtd_dists_finish`): lpips_each /
+lpips_per_slice / compute_LPIPS and dists_each / dists_per_slice / compute_DISTS (engine.test_MTD_GAN_Ours under
+`model.perceptual_vgg16` with `model.test_lpips` / `model.test_dists`).  The learned weights are the caller's too (lpips_weights /
+dists_weights)."""
 import functools
 import math
 
@@ -473,6 +481,53 @@ def patch_gram_l1_each(x, y, out=None, out_stride=1):
     return out
 
 
+def l2pool3x3s2(x):
+    """DISTS's L2Pool2d(3, stride 2, padding 1) of a contiguous NHWC fp32 map: sqrt(hann3x3 * x^2 + 1e-12), ceil(H / 2) x ceil(W / 2)
+    outputs (mtd_l2pool3x3s2)."""
+    B, H, W, Cc = x.shape
+    out = torch.empty((B, (H + 1) // 2, (W + 1) // 2, Cc), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().mtd_l2pool3x3s2(x.data_ptr(), out.data_ptr(), B, H, W, Cc, K.stream_ptr()), "mtd_l2pool3x3s2")
+    return out
+
+
+def _vgg_walk(layers, t, taps, pool_after, pool):
+    """The conv / ReLU / pool / tap walk of a torchvision VGG `features` stack on an NHWC chunk t: `layers` are (features index,
+    weight (N, C, 3, 3), bias) of the 3 x 3 convs in order, a ReLU follows each at index + 1; the map is tapped where that index
+    is in `taps` and pooled by `pool` where it is in `pool_after`.  Returns the tapped maps."""
+    maps = []
+    for idx, w, b in layers:
+        B, H, W, Cc = t.shape
+        N = w.shape[0]
+        out = torch.empty((B, H, W, N), dtype=torch.float32, device=t.device)
+        K.conv(t, w, K.geom_fwd(B, H, W, 3, 1, 1), N, Cc, Cc * 9, 9, out, bias=b, act=_lib.ACT_RELU)
+        t = out
+        if idx + 1 in taps:
+            maps.append(t)
+        if idx + 1 in pool_after:
+            t = pool(t)
+    return maps
+
+
+def _vgg_state(name, weights, convs):
+    """The (weight, bias) pairs of `convs` from a torchvision-layout state dict or a path to one; ValueError for a missing key or
+    a wrong shape."""
+    if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
+        weights = torch.load(weights, map_location="cpu", weights_only=True)
+    pairs = []
+    for idx, cin, cout in convs:
+        got = []
+        for leaf, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
+            key = f"features.{idx}.{leaf}"
+            if key not in weights:
+                raise ValueError(f"{name}: the state dict has no {key!r}")
+            t = weights[key]
+            if not torch.is_tensor(t) or tuple(t.shape) != shape:
+                raise ValueError(f"{name}: {key!r} has shape {tuple(getattr(t, 'shape', ()))}, expected {shape}")
+            got.append(t.detach())
+        pairs.append((idx, got[0], got[1]))
+    return pairs
+
+
 class VGG19Features:
     """The feature part of torchvision's VGG-19 up to relu5_1 on the HIP conv kernels, for single-channel images.
 
@@ -482,20 +537,8 @@ class VGG19Features:
     its three input-channel slices are summed once, here.  The weights go to the device of the first call's input, once."""
 
     def __init__(self, weights):
-        if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
-            weights = torch.load(weights, map_location="cpu", weights_only=True)
         self.layers = []                     # (features index, weight (N, C, 3, 3), bias (N,)) in fp32, first layer folded
-        for idx, cin, cout in _VGG19_CONVS:
-            got = []
-            for leaf, shape in (("weight", (cout, cin, 3, 3)), ("bias", (cout,))):
-                key = f"features.{idx}.{leaf}"
-                if key not in weights:
-                    raise ValueError(f"VGG19Features: the state dict has no {key!r}")
-                t = weights[key]
-                if not torch.is_tensor(t) or tuple(t.shape) != shape:
-                    raise ValueError(f"VGG19Features: {key!r} has shape {tuple(getattr(t, 'shape', ()))}, expected {shape}")
-                got.append(t.detach())
-            w, b = got
+        for idx, w, b in _vgg_state("VGG19Features", weights, _VGG19_CONVS):
             if idx == 0:
                 w = w.double().sum(dim=1, keepdim=True)
             self.layers.append((idx, w.float().contiguous(), b.float().contiguous()))
@@ -510,19 +553,7 @@ class VGG19Features:
 
     def _chunk(self, x):
         """The five maps of one chunk of images, (B, H, W, 1) in NHWC."""
-        maps = []
-        t = x
-        for idx, w, b in self.layers:
-            B, H, W, Cc = t.shape
-            N = w.shape[0]
-            out = torch.empty((B, H, W, N), dtype=torch.float32, device=t.device)
-            K.conv(t, w, K.geom_fwd(B, H, W, 3, 1, 1), N, Cc, Cc * 9, 9, out, bias=b, act=_lib.ACT_RELU)
-            t = out
-            if idx + 1 in _VGG19_TAPS:
-                maps.append(t)
-            if idx + 1 in _VGG19_POOL_AFTER:
-                t = maxpool2x2(t)
-        return maps
+        return _vgg_walk(self.layers, x, _VGG19_TAPS, _VGG19_POOL_AFTER, maxpool2x2)
 
     @torch.no_grad()
     def __call__(self, x):
@@ -683,8 +714,303 @@ def perceptual_metrics_per_slice(input, target, pred, vgg):
     return torch.cat([pl[0:1], zero, pl[1:2], _tml_each(levels)])
 
 
+# ================================================================================================ LPIPS, DISTS
+# torchvision vgg16().features: index of each conv -> (C_in, C_out); ReLU follows at index + 1
+_VGG16_CONVS = ((0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256),
+                (17, 256, 512), (19, 512, 512), (21, 512, 512), (24, 512, 512), (26, 512, 512), (28, 512, 512))
+_VGG16_POOL_AFTER = (3, 8, 15, 22)          # the pools at indices 4, 9, 16, 23 (the one at 30 lies behind the last tap)
+_VGG16_TAPS = (3, 8, 15, 22, 29)            # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 (perceptual.py: lpips_layers, dists_layers)
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+LPIPS_CHANNELS = (64, 128, 256, 512, 512)
+DISTS_CHANNELS = (3, 64, 128, 256, 512, 512)
+LPIPS_DISTANCES = ("mse", "mae")            # MTD_LPIPS_MSE / MTD_LPIPS_MAE
+
+
+def vgg16_first_layer(weight, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """The first conv of VGG-16 on a grey image x normalised per channel, (x - mean_c) / std_c, as a conv on the two channels
+    (x, 1): (N, 3, 3, 3) -> (N, 2, 3, 3) float64 with [:, 0] = sum_c w_c / std_c and [:, 1] = -sum_c w_c mean_c / std_c.  Zero
+    padding then pads both channels, which is what the reference's padding after the normalisation does: the constant part is
+    NOT a bias, it is absent where a tap lies outside the image.  mean and std are rounded to float32 first: piq holds them as
+    float32 tensors whatever the image's dtype."""
+    w = weight.double()
+    m = torch.tensor(mean, dtype=torch.float32).double().view(1, 3, 1, 1)
+    sd = torch.tensor(std, dtype=torch.float32).double().view(1, 3, 1, 1)
+    return torch.cat([(w / sd).sum(dim=1, keepdim=True), -(w * m / sd).sum(dim=1, keepdim=True)], dim=1)
+
+
+class VGG16Features:
+    """The feature part of torchvision's VGG-16 up to relu5_3 on the HIP conv kernels, for single-channel images, as piq's LPIPS
+    and DISTS use it (module/piq/perceptual.py): the grey image is broadcast against the three ImageNet constants, (x - mean) /
+    std, and tapped after relu1_2, relu2_2, relu3_3, relu4_3, relu5_3.
+
+    `weights`: a state dict in torchvision's `vgg16` key layout (features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias};
+    other keys are ignored) or a path to one (read with torch.load(..., weights_only=True)); no pretrained weights ship with this
+    package.  The normalisation is folded into the first layer exactly (vgg16_first_layer: two input channels, the image and
+    ones, in float64 on the host).  The weights go to the device of the first call's input, once."""
+
+    def __init__(self, weights, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+        if len(mean) != 3 or len(std) != 3 or not all(float(v) > 0 for v in std):
+            raise ValueError(f"VGG16Features: three means and three positive stds expected, got {mean!r}, {std!r}")
+        self.layers = []                     # (features index, weight (N, C, 3, 3), bias (N,)) in fp32, first layer folded to (x, 1)
+        for idx, w, b in _vgg_state("VGG16Features", weights, _VGG16_CONVS):
+            if idx == 0:
+                w = vgg16_first_layer(w, mean, std)
+            self.layers.append((idx, w.float().contiguous(), b.float().contiguous()))
+        self._device = None
+
+    def to(self, device):
+        device = torch.device(device)
+        if self._device != device:
+            self.layers = [(i, w.to(device), b.to(device)) for i, w, b in self.layers]
+            self._device = device
+        return self
+
+    @torch.no_grad()
+    def __call__(self, x, pool="max"):
+        """x: (B, 1, H, W) fp32 CUDA, H, W >= 16.  Returns the NHWC maps relu1_2 ... relu5_3 with 64, 128, 256, 512, 512 channels.
+        pool="max": nn.MaxPool2d(2, 2), sides H, H//2, H//4 ... (floor); pool="l2": DISTS's L2Pool2d(3, 2, 1), sides H,
+        ceil(H/2), ... (ceil at every pool)."""
+        if pool not in ("max", "l2"):
+            raise ValueError(f"VGG16Features: pool must be 'max' or 'l2', got {pool!r}")
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise AssertionError("VGG16Features expects a (B,1,H,W) tensor")
+        if not x.is_cuda:
+            raise RuntimeError("VGG16Features: HIP path needs CUDA tensors (no CPU fallback)")
+        B, _, H, W = x.shape
+        if H < 16 or W < 16:
+            raise ValueError(f"VGG16Features: images of at least 16 x 16 expected (four pools before relu5_3), got {H} x {W}")
+        per_image = H * W * 64 * 4                   # relu1_2, the largest map
+        if per_image > _MAX_MAP_BYTES:
+            raise ValueError(f"VGG16Features: a {H} x {W} image gives a first feature map of 2^31 bytes or more")
+        self.to(x.device)
+        x = x.detach().contiguous().float().reshape(B, H, W, 1)
+        x = torch.cat([x, torch.ones_like(x)], dim=3)                  # the channels (x, 1) of the folded first layer
+        pool_fn = maxpool2x2 if pool == "max" else l2pool3x3s2
+        step = max(1, _MAX_MAP_BYTES // per_image)
+        if B <= step:
+            return _vgg_walk(self.layers, x, _VGG16_TAPS, _VGG16_POOL_AFTER, pool_fn)
+        parts = [_vgg_walk(self.layers, x[i:i + step], _VGG16_TAPS, _VGG16_POOL_AFTER, pool_fn) for i in range(0, B, step)]
+        return [torch.cat([p[lvl] for p in parts]) for lvl in range(5)]
+
+
+def _load_weights_file(obj):
+    if isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__"):
+        return torch.load(obj, map_location="cpu", weights_only=True)
+    return obj
+
+
+def lpips_weights(obj):
+    """LPIPS's linear-layer weights as one float64 table of 64 + 128 + 256 + 512 + 512 = 1472 entries (level after level, on the
+    device the entries came from): `obj` is a list / tuple of five tensors with 64, 128, 256, 512, 512 elements of any shape (piq's
+    lpips_weights.pt holds them as (1, C, 1, 1)), a path to such a file, or a table this function returned.  ValueError with the
+    offending shape otherwise.  The published file was never seen here: the layout is the one module/piq/perceptual.py reads."""
+    obj = _load_weights_file(obj)
+    total = sum(LPIPS_CHANNELS)
+    if torch.is_tensor(obj) and obj.dtype == torch.float64 and obj.dim() == 1 and obj.numel() == total:
+        return obj.contiguous()
+    if not isinstance(obj, (list, tuple)) or len(obj) != 5 or not all(torch.is_tensor(t) for t in obj):
+        raise ValueError(f"lpips_weights: a list of five tensors with {LPIPS_CHANNELS} elements expected, got "
+                         f"{[tuple(t.shape) for t in obj] if isinstance(obj, (list, tuple)) and all(torch.is_tensor(t) for t in obj) else type(obj).__name__}")
+    for t, n in zip(obj, LPIPS_CHANNELS):
+        if t.numel() != n or not (t.is_floating_point()):
+            raise ValueError(f"lpips_weights: a floating-point tensor of {n} elements expected, got shape {tuple(t.shape)} {t.dtype}")
+    return torch.cat([t.detach().double().flatten() for t in obj]).contiguous()
+
+
+def dists_weights(obj):
+    """DISTS's alpha and beta as one (2, 1475) float64 table (row 0 alpha, row 1 beta; 1475 = 3 + 64 + 128 + 256 + 512 + 512, the
+    first three for the raw image): `obj` is a dict with `alpha` and `beta` of 1475 elements each in any shape (piq's
+    dists_weights.pt holds them as (1, 1475, 1, 1)), a path to such a file, or a table this function returned.  ValueError with the
+    offending shape otherwise.  The published file was never seen here: the layout is the one module/piq/perceptual.py reads."""
+    obj = _load_weights_file(obj)
+    total = sum(DISTS_CHANNELS)
+    if torch.is_tensor(obj) and obj.dtype == torch.float64 and tuple(obj.shape) == (2, total):
+        return obj.contiguous()
+    if not isinstance(obj, dict) or "alpha" not in obj or "beta" not in obj:
+        raise ValueError(f"dists_weights: a dict with 'alpha' and 'beta' of {total} elements each expected, got "
+                         f"{sorted(obj) if isinstance(obj, dict) else type(obj).__name__}")
+    rows = []
+    for name in ("alpha", "beta"):
+        t = obj[name]
+        if not torch.is_tensor(t) or t.numel() != total or not t.is_floating_point():
+            raise ValueError(f"dists_weights: {name!r} must be a floating-point tensor of {total} elements, got shape "
+                             f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t).__name__)}")
+        rows.append(t.detach().double().flatten())
+    return torch.stack(rows).contiguous()
+
+
+def lpips_level_each(t, a, b, weights, distance="mse", out=None, out_stride=1, other_stride=None):
+    """Per image i and other map o = a (k = 0), b (k = 1; b may be None): sum over pixels and channels of
+    w_c d(o_c / (|o| + 1e-10), t_c / (|t| + 1e-10)) of contiguous NHWC fp32 maps of one shape, C in {64, 128, 256, 512}, as device
+    doubles at out[k * other_stride + i * out_stride] (mtd_lpips_level_each); nothing else of `out` is written.  weights: C
+    float64 entries on the maps' device."""
+    if distance not in LPIPS_DISTANCES:
+        raise ValueError(f"lpips: distance must be one of {LPIPS_DISTANCES}, got {distance!r}")
+    maps = [m for m in (t, a, b) if m is not None]
+    if a is None or any(m.shape != t.shape or m.dim() != 4 or not m.is_cuda or not m.is_contiguous() or m.dtype != torch.float32 for m in maps):
+        raise ValueError("lpips_level_each: contiguous CUDA NHWC fp32 maps of one shape expected")
+    B, h, w, Cc = t.shape
+    if weights.dtype != torch.float64 or weights.numel() != Cc or not weights.is_cuda or not weights.is_contiguous():
+        raise ValueError(f"lpips_level_each: {Cc} contiguous float64 weights on the device expected")
+    n = 2 if b is not None else 1
+    if other_stride is None:
+        other_stride = B * out_stride
+    need = (n - 1) * other_stride + (B - 1) * out_stride + 1
+    if out is None:
+        out = torch.zeros(need, dtype=torch.float64, device=t.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < need or out_stride < 1 or other_stride < 0:
+        raise ValueError("lpips_level_each: `out` must be a contiguous float64 tensor that holds every addressed element")
+    L = _lib.lib()
+    nbytes = L.mtd_lpips_level_ws_bytes(B, h, w, Cc)
+    if not nbytes:
+        raise ValueError(f"lpips_level_each: maps of shape {tuple(t.shape)} are not taken (C in 64, 128, 256, 512)")
+    ws = K.workspace(nbytes, t.device)
+    _lib.check(L.mtd_lpips_level_each(t.data_ptr(), a.data_ptr(), b.data_ptr() if b is not None else None, B, h, w, Cc, weights.data_ptr(),
+                                      LPIPS_DISTANCES.index(distance), out.data_ptr(), out_stride, other_stride, ws.data_ptr(), K.stream_ptr()),
+               "mtd_lpips_level_each")
+    return out
+
+
+def channel_moments_each(t, a, b=None):
+    """(B, C, 2 + 3 n) float64 table of per-image, per-channel sums over the pixels of contiguous NHWC fp32 maps of one shape
+    (C = 1 or a multiple of 4 up to 1024): (sum t, sum t^2) and per other map o = a, b (b may be None) (sum o, sum o^2, sum o t)
+    (mtd_channel_moments_each)."""
+    maps = [m for m in (t, a, b) if m is not None]
+    if a is None or any(m.shape != t.shape or m.dim() != 4 or not m.is_cuda or not m.is_contiguous() or m.dtype != torch.float32 for m in maps):
+        raise ValueError("channel_moments_each: contiguous CUDA NHWC fp32 maps of one shape expected")
+    B, h, w, Cc = t.shape
+    n = 2 if b is not None else 1
+    L = _lib.lib()
+    nbytes = L.mtd_channel_moments_ws_bytes(B, h, w, Cc, n)
+    if not nbytes:
+        raise ValueError(f"channel_moments_each: maps of shape {tuple(t.shape)} are not taken (C = 1 or a multiple of 4 up to 1024)")
+    out = torch.empty((B, Cc, 2 + 3 * n), dtype=torch.float64, device=t.device)
+    ws = K.workspace(nbytes, t.device)
+    _lib.check(L.mtd_channel_moments_each(t.data_ptr(), a.data_ptr(), b.data_ptr() if b is not None else None, B, h, w, Cc, out.data_ptr(),
+                                          ws.data_ptr(), K.stream_ptr()), "mtd_channel_moments_each")
+    return out
+
+
+def dists_finish(tables, pixels, weights, self_row=-1, parts=False):
+    """DISTS's closing formula on the six moment tables (channel_moments_each of the raw image and the five maps, one n and B):
+    (rows, B) float64 scores 1 - sum(alpha S1 + beta S2), rows = the others in order, plus, with self_row >= 0, a row at that
+    index for the target against itself (S1 = S2 = 1 exactly).  pixels: h * w per level; weights: dists_weights' table on the
+    device.  With parts=True also the (rows, B, 6) level sums (mtd_dists_finish)."""
+    import ctypes
+    if len(tables) != 6 or len(pixels) != 6:
+        raise ValueError("dists_finish: six tables and six pixel counts expected")
+    B, _, Kk = tables[0].shape
+    n = (Kk - 2) // 3
+    for tb, c in zip(tables, (1,) + DISTS_CHANNELS[1:]):
+        if tb.dtype != torch.float64 or tuple(tb.shape) != (B, c, Kk) or not tb.is_cuda or not tb.is_contiguous():
+            raise ValueError(f"dists_finish: a contiguous CUDA float64 table of shape {(B, c, Kk)} expected, got {tuple(tb.shape)}")
+    if weights.dtype != torch.float64 or tuple(weights.shape) != (2, sum(DISTS_CHANNELS)) or not weights.is_cuda or not weights.is_contiguous():
+        raise ValueError("dists_finish: dists_weights' (2, 1475) float64 table on the device expected")
+    rows = n + (1 if self_row >= 0 else 0)
+    dev = tables[0].device
+    out = torch.empty((rows, B), dtype=torch.float64, device=dev)
+    lv = torch.empty((rows, B, 6), dtype=torch.float64, device=dev) if parts else None
+    ptrs = (ctypes.c_void_p * 6)(*(tb.data_ptr() for tb in tables))
+    px = (ctypes.c_longlong * 6)(*(int(p) for p in pixels))
+    _lib.check(_lib.lib().mtd_dists_finish(ptrs, px, n, B, self_row, weights[0].data_ptr(), weights[1].data_ptr(), out.data_ptr(),
+                                           lv.data_ptr() if parts else None, K.stream_ptr()), "mtd_dists_finish")
+    return (out, lv) if parts else out
+
+
+def _vgg16_inputs(name, input, target, pred, vgg):
+    if not isinstance(vgg, VGG16Features):
+        raise TypeError(f"{name}: pass the feature network as vgg=VGG16Features(state_dict) (no pretrained weights ship with this package)")
+    for t in (input, target, pred):
+        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
+            raise AssertionError(f"{name} expects three (B,1,H,W) tensors of the same shape")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: HIP path needs CUDA tensors (no CPU fallback)")
+    H, W = target.shape[2:]
+    if H < 16 or W < 16:
+        raise ValueError(f"{name}: images of at least 16 x 16 expected, got {H} x {W}")
+
+
+@torch.no_grad()
+def lpips_each(input, target, pred, *, vgg, weights, distance="mse", parts=False):
+    """LPIPS (piq's LPIPS: VGG-16, unit-normalised features, learned channel weights, data_range 1; replace_pooling=False) of
+    every slice of (input, target, pred) against the same slice of target, without a host read: a (3, B) float64 device tensor,
+    rows input, gt, pred; the gt row is the constant 0 (no reduction is launched for it).  One network pass on the 3B stacked
+    images, one mtd_lpips_level_each per level (the target's map read once for both others), one launch weighs the levels by
+    1 / (h w).  With parts=True also the (3, B, 5) per-level values.  vgg: VGG16Features; weights: lpips_weights' table or any
+    form it takes; distance: "mse" (piq's default) or "mae".  H, W >= 16."""
+    import ctypes
+    _vgg16_inputs("lpips_each", input, target, pred, vgg)
+    if distance not in LPIPS_DISTANCES:
+        raise ValueError(f"lpips: distance must be one of {LPIPS_DISTANCES}, got {distance!r}")
+    B = target.shape[0]
+    dev = target.device
+    table = lpips_weights(weights).to(dev)
+    maps = vgg(torch.cat([target, input, pred]).float(), pool="max")
+    sums = torch.zeros((3, B, 5), dtype=torch.float64, device=dev)
+    scales = (ctypes.c_double * 5)()
+    c0 = 0
+    for lvl, m in enumerate(maps):
+        _, h, w, Cc = m.shape
+        scales[lvl] = 1.0 / float(h * w)
+        lpips_level_each(m[:B], m[B:2 * B], m[2 * B:], table[c0:c0 + Cc], distance, out=sums.view(-1)[lvl:], out_stride=5, other_stride=2 * B * 5)
+        c0 += Cc
+    out = torch.empty((3, B), dtype=torch.float64, device=dev)
+    lv = torch.empty((3, B, 5), dtype=torch.float64, device=dev) if parts else None
+    _lib.check(_lib.lib().mtd_scaled_sums_f64_f64(sums.data_ptr(), 3 * B, 5, scales, out.data_ptr(), lv.data_ptr() if parts else None, K.stream_ptr()),
+               "mtd_scaled_sums_f64_f64")
+    return (out, lv) if parts else out
+
+
+@torch.no_grad()
+def dists_each(input, target, pred, *, vgg, weights, parts=False):
+    """DISTS (piq's DISTS: VGG-16 with L2 pooling, the raw image as level 0, structure and texture similarity of the per-channel
+    moments, data_range 1) of every slice of (input, target, pred) against the same slice of target, without a host read: a
+    (3, B) float64 device tensor, rows input, gt, pred; the gt row is the constant 1 - sum(alpha + beta) of the finish arithmetic.
+    One network pass (pool="l2") on the 3B stacked images, one mtd_channel_moments_each per level, one mtd_dists_finish.  With
+    parts=True also the (3, B, 6) per-level sums of alpha S1 + beta S2.  vgg: VGG16Features; weights: dists_weights' table or any
+    form it takes.  H, W >= 16."""
+    _vgg16_inputs("dists_each", input, target, pred, vgg)
+    B, _, H, W = target.shape
+    dev = target.device
+    table = dists_weights(weights).to(dev)
+    stacked = torch.cat([target, input, pred]).float().contiguous()
+    maps = [stacked.reshape(3 * B, H, W, 1)] + vgg(stacked, pool="l2")
+    tables = [channel_moments_each(m[:B], m[B:2 * B], m[2 * B:]) for m in maps]
+    return dists_finish(tables, [m.shape[1] * m.shape[2] for m in maps], table, self_row=1, parts=parts)
+
+
+def _who_triples(vals):
+    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+
+
+def lpips_per_slice(input, target, pred, **kw):
+    """lpips_each as host numbers: a list of B (input, gt, pred) triples.  One device -> host copy for the batch."""
+    return _who_triples(lpips_each(input, target, pred, **kw).tolist())
+
+
+def dists_per_slice(input, target, pred, **kw):
+    """dists_each as host numbers: a list of B (input, gt, pred) triples.  One device -> host copy for the batch."""
+    return _who_triples(dists_each(input, target, pred, **kw).tolist())
+
+
+def compute_LPIPS(input, target, pred, data_range=1.0, **kw):
+    """piq's LPIPS(reduction='mean')(a, target) for a = input, target, pred: a triple of 0-dim float64 device tensors, each the mean
+    over the batch of the per-image scores.  Keywords as lpips_each (vgg, weights, distance)."""
+    if data_range != 1.0:
+        raise NotImplementedError("lpips: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
+    return tuple(lpips_each(input, target, pred, **kw).mean(dim=1).unbind())
+
+
+def compute_DISTS(input, target, pred, data_range=1.0, **kw):
+    """piq's DISTS(reduction='mean')(a, target) likewise.  Keywords as dists_each (vgg, weights)."""
+    if data_range != 1.0:
+        raise NotImplementedError("dists: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
+    return tuple(dists_each(input, target, pred, **kw).mean(dim=1).unbind())
+
+
 # ================================================================================================ FID
-FID_MAX_ITERS = 100                         # _sqrtm_newton_schulz(num_iters=100), fid.py:24
+FID_MAX_ITERS = 100                        # _sqrtm_newton_schulz(num_iters=100), fid.py:24
 FID_EPS = 1e-6                              # _compute_fid(eps=1e-6), fid.py:64
 
 
