@@ -123,15 +123,8 @@ __global__ __launch_bounds__(256) void wino_weights_kernel(const WinoWDesc* __re
                 const long long xs16 = (long long)(w.C / 16) * 3 * plane;
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
-                    const float t0 = t[a][0], t1 = t[a][1], t2 = t[a][2];
                     float u[6];
-                    if (PXr == 6) {
-                        const float e = (t0 + t2) * (1.f / 6.f), f = t1 * (1.f / 6.f);
-                        const float h = t0 * (1.f / 24.f) + t2 * (1.f / 6.f), k = t1 * (1.f / 12.f);
-                        u[0] = 0.25f * t0; u[1] = -e - f; u[2] = -e + f; u[3] = h + k; u[4] = h - k; u[5] = t2;
-                    } else {
-                        u[0] = t0; u[1] = 0.5f * (t0 + t1 + t2); u[2] = 0.5f * (t0 - t1 + t2); u[3] = t2; u[4] = u[5] = 0.f;
-                    }
+                    wino_w_cols(t[a][0], t[a][1], t[a][2], PXr, u);      // (the fp32 form's values, bit for bit)
                     for (int b = 0; b < PXr; ++b) {
                         unsigned hh, mm, ll;
                         w3_split(u[b], hh, mm, ll);

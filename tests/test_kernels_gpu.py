@@ -749,7 +749,8 @@ def _winograd_conv_case(K, B, Ci, Co, H, W, what, form, pipe="bf16x3"):
 def test_winograd_32_channel_form(hip_lib, case):
     """The generator's 32 -> 32 layers on whole-slice maps (side >= kernels.WINO_C32_MIN_HW = 128) run on the F(2x4, 3x3)
     form: the persistent kernel of csrc/conv_wino_c32.h (weights in registers, two half-steps per 256-pixel block; one residual
-    operand at most) or, with a mask, the general kernel's 32-channel workgroups (wino_conv_kernel<1, false, 6>).  Forward conv /
+    operand at most; with a mask its MASKED form -- every case here satisfies wino_c32_takes, the general kernel's 32-channel
+    workgroups, wino_conv_kernel<1, false, 6>, are reached by tests/test_wino_kernels_gpu.py).  Forward conv /
     ConvTranspose gather with the epilogues the inference schedule uses -- relu(conv + b) + x (MTD_ACT_RELU_ADD),
     relu(conv + b + skip), relu(conv + b) -- and the others, on whole blocks, ragged last blocks (136 x 132 x 3, 130 x 140 x 5) and
     the bench's own size, against torch on the CPU in float64 and against the halo-tile implicit GEMM on the same inputs.  On a 64 x 64 map the
