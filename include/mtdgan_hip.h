@@ -613,6 +613,39 @@ int mtd_fsim_each(const void* const* srcs, int na, const void* target, int B, in
                   const float* filters, const double* consts, double* out, double* parts, void* ws, void* stream);
 int mtd_fsim_median(const float* values, int n, int count, float* out, void* stream);
 
+/* ---- visual saliency-induced index and mean deviation similarity index of the test loop (module/piq: vsi.py vsi, mdsi.py mdsi)
+ * -- DESIGN 3.19.  Single-channel fp32 images (B, H, W) in [0, 1] (data_range 1; piq copies the grey channel three times), na in
+ * 1..3 sources srcs[k] against one target, image by image.  k is piq's pooling kernel max(1, round(min(H, W) / 256)) with
+ * Python's round (half to even), computed by the caller; the pooled map has (H + k - 1) / k x (W + k - 1) / k pixels (VSI pads
+ * [k / 2, (k - 1) / 2] in replicate mode, MDSI [(k - 1) / 2, k / 2] with zeros).  `options` is read on the host during the call,
+ * as srcs is (its first na entries).  A source whose pointer equals the target's shares the target's maps (VSI).  Everything
+ * but the 256 x 256 transforms of VSI's saliency map (fp32, radix-2 passes in LDS) is double, every per-image sum in a fixed
+ * order: an image's numbers depend neither on the batch nor on its source slot.  The batch is walked in chunks sized so that
+ * the workspace (the _ws_bytes query) stays within 64 MiB (VSI) / 16 MiB (MDSI).
+ * mtd_vsi_each: log_gabor: device, (256, 256) fp32, zero frequency at [0, 0] (piq's _log_gabor); options: c1, c2, c3, alpha, beta,
+ *   sigma_d, sigma_c.  out: (na, B) doubles.  parts (optional, may be null): (na, B, MTD_VSI_PARTS) doubles: num, den, the sums of
+ *   the source's pooled saliency and gradient maps, the minimum and maximum of its saliency map before it is stretched to [0, 1].
+ * mtd_mdsi_each: options: c1, c2, c3, alpha, beta, gamma, rho, q, o; mult: 0 combination 'sum', 1 'mult'.  out: (na, B) doubles.
+ *   parts (optional): (na, B, MTD_MDSI_PARTS) doubles: the means of the real and imaginary part of gcs^q and the sum of
+ *   |gcs^q - mean|^rho.
+ * Null pointers, na outside 1..3, B < 1, k outside 1..8, a side outside MTD_*_MIN_SIDE .. MTD_*_MAX_SIDE, an option that is not
+ * finite, a c1, c2, c3 (or MDSI's rho) that is not positive, a zero sigma, another mult: MTD_EINVAL before any launch (the
+ * _ws_bytes query then returns 0). */
+#define MTD_VSI_MIN_SIDE 16
+#define MTD_VSI_MAX_SIDE 1024
+#define MTD_VSI_PARTS 6
+#define MTD_VSI_OPTIONS 7
+#define MTD_MDSI_MIN_SIDE 16
+#define MTD_MDSI_MAX_SIDE 1024
+#define MTD_MDSI_PARTS 3
+#define MTD_MDSI_OPTIONS 9
+size_t mtd_vsi_ws_bytes(int na, int B, int H, int W, int k);
+int mtd_vsi_each(const void* const* srcs, int na, const void* target, int B, int H, int W, int k, const float* log_gabor,
+                 const double* options, double* out, double* parts, void* ws, void* stream);
+size_t mtd_mdsi_ws_bytes(int na, int B, int H, int W, int k);
+int mtd_mdsi_each(const void* const* srcs, int na, const void* target, int B, int H, int W, int k, const double* options, int mult,
+                  double* out, double* parts, void* ws, void* stream);
+
 /* ---- perceptual metrics of the test loop (metrics.py:43-168: PL and TML on VGG-19 features; engine.py:139-140) ------
  * The convolutions of the feature stack are mtd_conv_* launches; these are the other pieces.  Maps are contiguous NHWC fp32,
  * 16-byte aligned (MTD_EALIGN).

@@ -289,6 +289,10 @@ def lib():
     sig("mtd_fsim_ws_bytes", sz, ci, ci, ci, ci, ci, ci)
     sig("mtd_fsim_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, vp)
     sig("mtd_fsim_median", ci, vp, ci, ci, vp, vp)
+    sig("mtd_vsi_ws_bytes", sz, ci, ci, ci, ci, ci)
+    sig("mtd_vsi_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, vp, C.POINTER(C.c_double), vp, vp, vp, vp)
+    sig("mtd_mdsi_ws_bytes", sz, ci, ci, ci, ci, ci)
+    sig("mtd_mdsi_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, C.POINTER(C.c_double), ci, vp, vp, vp, vp)
     sig("mtd_maxpool2x2", ci, vp, vp, ci, ci, ci, ci, vp)
     sig("mtd_patch_gram_l1_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_patch_gram_l1", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
@@ -394,6 +398,7 @@ EXPORTS = [
     "mtd_iqa_ws_bytes", "mtd_iqa_each",
     "mtd_haarpsi_ws_bytes", "mtd_haarpsi_each",
     "mtd_fsim_ws_bytes", "mtd_fsim_each", "mtd_fsim_median",
+    "mtd_vsi_ws_bytes", "mtd_vsi_each", "mtd_mdsi_ws_bytes", "mtd_mdsi_each",
     "mtd_l2pool3x3s2", "mtd_lpips_level_ws_bytes", "mtd_lpips_level_each", "mtd_scaled_sums_f64_f64",
     "mtd_channel_moments_ws_bytes", "mtd_channel_moments_each", "mtd_dists_finish",
 ]

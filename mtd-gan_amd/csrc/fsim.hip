@@ -16,6 +16,7 @@
 // Launches per chunk of the batch: rows forward (pooling on load), columns forward, filter + columns inverse, rows inverse +
 // energy (one workgroup per orientation and row tile), thresholds, combine, finish.  The responses themselves are never stored; the column-transformed filtered spectra are.
 #include "common.h"
+#include "lds_fft.h"          // fs_brev, fs_twiddles, fs_lds_fft
 #include <float.h>
 #include <math.h>
 
@@ -46,44 +47,6 @@ __device__ __forceinline__ float fs_pixel(const float* __restrict__ img, int W, 
     for (int dy = 0; dy < ks; ++dy)
         for (int dx = 0; dx < ks; ++dx) s += __fmul_rn(255.f, p[(long long)dy * W + dx]);
     return __fdiv_rn(s, (float)(ks * ks));
-}
-
-__device__ __forceinline__ int fs_brev(int i, int ln) { return (int)(__brev((unsigned)i) >> (32 - ln)); }
-
-// tw[t] = e^{2 pi i t / n}, t < n / 2 <= 256, rounded from double.
-__device__ __forceinline__ void fs_twiddles(float2* tw, int n) {
-    const int t = threadIdx.x;
-    if (t < n / 2) {
-        double s, c;
-        sincospi(2.0 * (double)t / (double)n, &s, &c);
-        tw[t] = make_float2((float)c, (float)s);
-    }
-}
-
-// In-place transforms of `lines` lines of n = 2^ln complex points in LDS (line l at buf + l * ld), by the 256 threads of the
-// workgroup: X[k] = sum_j x[j] e^{SIGN 2 pi i j k / n}, unnormalised.  Radix-2 decimation in time: the input is in bit-reversed
-// order, the output in natural order.  The caller has synchronised after its stores (and after fs_twiddles); the function ends
-// with a barrier.
-template <int SIGN>
-__device__ __forceinline__ void fs_lds_fft(float2* buf, int lines, int ln, int ld, const float2* tw) {
-    const int total = lines << (ln - 1);
-    const int jm = (1 << (ln - 1)) - 1;
-    for (int s = 1; s <= ln; ++s) {
-        const int half = 1 << (s - 1);
-        for (int e = threadIdx.x; e < total; e += 256) {
-            const int l = e >> (ln - 1), j = e & jm;
-            const int k = j & (half - 1);
-            float2* p = buf + l * ld + ((j >> (s - 1)) << s) + k;
-            const float2 w = tw[k << (ln - s)];
-            const float2 u = p[0], v = p[half];
-            float tr, ti;
-            if (SIGN > 0) { tr = v.x * w.x - v.y * w.y; ti = v.x * w.y + v.y * w.x; }
-            else { tr = v.x * w.x + v.y * w.y; ti = v.y * w.x - v.x * w.y; }
-            p[0] = make_float2(u.x + tr, u.y + ti);
-            p[half] = make_float2(u.x - tr, u.y - ti);
-        }
-        __syncthreads();
-    }
 }
 
 // ---- 1. pool on load + forward rows.  grid (h / L, sets * Bc); slot = set * Bc + image of the chunk.

@@ -314,6 +314,46 @@ def _fsim_update(triple, meters):
     return (triple[2],)
 
 
+def _vsi_option(model):
+    """`model.test_vsi` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.vsi_each's defaults); a dict with keys
+    from c1, c2, c3, alpha, beta, omega_0, sigma_f, sigma_d, sigma_c that metrics.vsi_check_options accepts -> those keyword
+    arguments.  Anything else: ValueError, before anything runs on the device."""
+    from . import metrics as M
+    cfg = getattr(model, "test_vsi", None)
+    if not cfg:
+        return None
+    if cfg is True:
+        return {}
+    try:
+        if not isinstance(cfg, dict) or set(cfg) - set(M.VSI_OPTIONS):
+            raise ValueError("not a dict of the options")
+        M.vsi_check_options(**cfg)
+    except ValueError as e:
+        raise ValueError("model.test_vsi: True or a dict with the keys c1, c2, c3, omega_0, sigma_f, sigma_d, sigma_c (positive numbers), "
+                         f"alpha, beta (numbers); got {cfg!r} ({e})") from None
+    return dict(cfg)
+
+
+def _mdsi_option(model):
+    """`model.test_mdsi` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.mdsi_each's defaults); a dict with keys
+    from c1, c2, c3, combination, alpha, beta, gamma, rho, q, o that metrics.mdsi_check_options accepts -> those keyword arguments.
+    Anything else: ValueError, before anything runs on the device."""
+    from . import metrics as M
+    cfg = getattr(model, "test_mdsi", None)
+    if not cfg:
+        return None
+    if cfg is True:
+        return {}
+    try:
+        if not isinstance(cfg, dict) or set(cfg) - set(M.MDSI_OPTIONS):
+            raise ValueError("not a dict of the options")
+        M.mdsi_check_options(**cfg)
+    except ValueError as e:
+        raise ValueError("model.test_mdsi: True or a dict with the keys c1, c2, c3, rho (positive numbers), combination ('sum' or 'mult'), "
+                         f"alpha, beta, gamma, q, o (numbers); got {cfg!r} ({e})") from None
+    return dict(cfg)
+
+
 def _lpips_option(model):
     """`model.test_lpips` of test_MTD_GAN_Ours: absent or falsy -> None; LPIPS's linear-layer weights in a form
     metrics.lpips_weights takes (five tensors, or a path), or `dict(weights=..., distance="mse" | "mae")` -> the keyword arguments
@@ -378,7 +418,7 @@ def _iqa_update(iqa, triples, meters):
 
 
 def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa=None, haarpsi=None, fsim=None, lpips=None,
-                          dists=None):
+                          dists=None, vsi=None, mdsi=None):
     """One loader batch of test_MTD_GAN_Ours under `model.test_per_slice`: B meter updates and B rows from one host read."""
     from . import kernels as K, metrics as M
     B, _, H, W = x.shape
@@ -399,6 +439,10 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
         parts.append(M.lpips_each(x, y, clipped, **lpips).flatten())            # (who, slice) float64, behind the FSIM block
     if dists is not None:
         parts.append(M.dists_each(x, y, clipped, **dists).flatten())            # (who, slice) float64, behind the LPIPS block
+    if vsi is not None:
+        parts.append(M.vsi_each(x, y, clipped, **vsi).flatten())                # (who, slice) float64, behind the DISTS block
+    if mdsi is not None:
+        parts.append(M.mdsi_each(x, y, clipped, **mdsi).flatten())              # (who, slice) float64, behind the VSI block
     vals = torch.cat(parts).tolist()                  # every per-slice value of the batch in one device -> host copy
     l1 = vals[:B]
     sums = [[vals[B + (k * B + i) * 2:B + (k * B + i) * 2 + 2] for i in range(B)] for k in range(3)]
@@ -409,6 +453,8 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
     q2 = q1 + (3 * B if haarpsi is not None else 0)   # where the FSIM block starts
     q3 = q2 + (3 * B if fsim is not None else 0)      # where the LPIPS block starts
     q4 = q3 + (3 * B if lpips is not None else 0)     # where the DISTS block starts
+    q5 = q4 + (3 * B if dists is not None else 0)     # where the VSI block starts
+    q6 = q5 + (3 * B if vsi is not None else 0)       # where the MDSI block starts
     paths = batch_data.get("path_n_20") if isinstance(batch_data, dict) else None
     for i in range(B):
         meters.setdefault("L1_loss", _Meter()).update(l1[i], 1)
@@ -430,6 +476,10 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
             more += _named_update("lpips", tuple(vals[q3 + k * B + i] for k in range(3)), meters)
         if dists is not None:
             more += _named_update("dists", tuple(vals[q4 + k * B + i] for k in range(3)), meters)
+        if vsi is not None:
+            more += _named_update("vsi", tuple(vals[q5 + k * B + i] for k in range(3)), meters)
+        if mdsi is not None:
+            more += _named_update("mdsi", tuple(vals[q6 + k * B + i] for k in range(3)), meters)
         path = paths[i] if paths is not None else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][i][2], pm["psnr"][i][2], pm["ssim"][i][2]) + more)
 
@@ -641,6 +691,14 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     in the batch's one device -> host copy, behind the FSIM block.  Slices of at least 16 x 16.  Weights in another form, another
     distance, or either option without `perceptual_vgg16` are refused (ValueError) before anything runs; without the attributes
     (or with None / False) nothing changes.
+    `model.test_vsi = True` (or a dict of c1, c2, c3, alpha, beta, omega_0, sigma_f, sigma_d, sigma_c) and `model.test_mdsi = True`
+    (or a dict of c1, c2, c3, combination, alpha, beta, gamma, rho, q, o) add the reference's vendored piq metrics VSI
+    and MDSI of (input, gt, clipped prediction) against gt on the HIP kernels of csrc/vsi.hip and csrc/mdsi.hip (metrics.vsi_each /
+    mdsi_each): the result gains {input,gt,pred}_vsi and {input,gt,pred}_mdsi after the DISTS keys (before the FID / KID keys) and
+    the CSV the columns VSI and MDSI after DISTS, holding the prediction's values.  On the default path a batch gives one value
+    per image set (the mean over its slices, one more host read each); under `test_per_slice` the 3 B values of each travel in
+    the batch's one device -> host copy, behind the DISTS block.  Slices with sides in 16..1024 (ValueError otherwise).  Any other
+    value of either attribute is refused (ValueError) before anything runs; without them (or with falsy values) nothing changes.
     `model.test_kid = True` (or a dict of metrics.kid_distance64's keyword arguments) adds piq's Kernel Inception
     Distance after the loop, from the same feature rows as FID and therefore only with `model.fid_features` (ValueError
     otherwise, before anything runs): the result gains input_kid / gt_kid / pred_kid behind the FID keys (metrics.compute_KID:
@@ -653,6 +711,8 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     _fsim_option(model)
     _lpips_option(model)
     _dists_option(model)
+    _vsi_option(model)
+    _mdsi_option(model)
     _kid_option(model)
     stored = _StoredInput.from_model(model)
     dcm = _DcmSink.from_model(model, stored)
@@ -678,6 +738,8 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
     fsim = _fsim_option(model)
     lpips = _lpips_option(model)
     dists = _dists_option(model)
+    vsi = _vsi_option(model)
+    mdsi = _mdsi_option(model)
     for opt in (lpips, dists):                           # the small weight tables go to the device once, not once per batch
         if opt is not None:
             opt["weights"] = opt["weights"].to(device)
@@ -705,7 +767,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         if dcm is not None:
             slices = dcm.begin(pred, words, table)             # likewise
         if per_slice:
-            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa, haarpsi, fsim, lpips, dists)
+            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa, haarpsi, fsim, lpips, dists, vsi, mdsi)
             if png is not None:
                 png.submit(images, batch_data, k0)
             if dcm is not None:
@@ -739,6 +801,10 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
             more += _named_update("lpips", tuple(M.lpips_each(x, y, clipped, **lpips).mean(dim=1).tolist()), meters)
         if dists is not None:        # likewise
             more += _named_update("dists", tuple(M.dists_each(x, y, clipped, **dists).mean(dim=1).tolist()), meters)
+        if vsi is not None:          # likewise
+            more += _named_update("vsi", tuple(M.vsi_each(x, y, clipped, **vsi).mean(dim=1).tolist()), meters)
+        if mdsi is not None:         # likewise
+            more += _named_update("mdsi", tuple(M.mdsi_each(x, y, clipped, **mdsi).mean(dim=1).tolist()), meters)
         path = batch_data.get("path_n_20", [f"slice_{len(rows)}"])[0] if isinstance(batch_data, dict) else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]) + more)
         if png is not None:
@@ -751,7 +817,8 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         with open(os.path.join(save_dir, "pred_results.csv"), "w") as f:
             f.write((",PATH,PL,TML,RMSE,PSNR,SSIM" if vgg is not None else ",PATH,RMSE,PSNR,SSIM")
                     + "".join("," + _IQA_COLUMNS[n] for n in iqa or ()) + (",HaarPSI" if haarpsi is not None else "") + (",FSIM" if fsim is not None else "")
-                    + (",LPIPS" if lpips is not None else "") + (",DISTS" if dists is not None else "") + "\n")
+                    + (",LPIPS" if lpips is not None else "") + (",DISTS" if dists is not None else "")
+                    + (",VSI" if vsi is not None else "") + (",MDSI" if mdsi is not None else "") + "\n")
             for i, r in enumerate(rows):
                 f.write(f"{i}," + ",".join(str(v) for v in r) + "\n")
     if fid_features is not None:

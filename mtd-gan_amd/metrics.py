@@ -36,6 +36,12 @@ image by image on the HIP kernels of csrc/fsim.hip (`mtd_fsim_each`; DESIGN 3.17
 (engine.test_MTD_GAN_Ours under `model.test_fsim`).  The log-Gabor filter table and its three noise constants are built on the
 host once per (pooled size, options) and uploaded once per device (fsim_filter_table / fsim_constants).
 
+VSI (module/piq/vsi.py: vsi) and MDSI (module/piq/mdsi.py: mdsi), the visual saliency-induced index and the mean deviation
+similarity index, image by image on the HIP kernels of csrc/vsi.hip and csrc/mdsi.hip (`mtd_vsi_each`, `mtd_mdsi_each`; DESIGN
+3.19): vsi_each / vsi_per_slice / compute_VSI and mdsi_each / mdsi_per_slice / compute_MDSI (engine.test_MTD_GAN_Ours under
+`model.test_vsi` / `model.test_mdsi`).  SDSP's log-Gabor table is built on the host once per (omega_0, sigma_f) and uploaded once
+per device (vsi_log_gabor_table).
+
 LPIPS and DISTS (module/piq/perceptual.py: LPIPS and DISTS on torchvision's VGG-16 with ImageNet normalisation) image by image
 (DESIGN 3.18): the feature stack is `VGG16Features`, built like `VGG19Features` from a state dict the caller hands over, with the
 normalisation folded exactly into its first layer and max or L2 pooling (`mtd_l2pool3x3s2`); the reductions over the maps run on
@@ -425,6 +431,172 @@ def compute_FSIM(input, target, pred, data_range=1.0, **kw):
     if data_range != 1.0:
         raise NotImplementedError("fsim: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
     return tuple(fsim_each(input, target, pred, **kw).mean(dim=1).tolist())
+
+
+# ================================================================================================ VSI and MDSI
+VSI_MIN_SIDE, VSI_MAX_SIDE = 16, 1024                           # of the image; any side in between (SDSP's transforms are always 256 x 256)
+VSI_PARTS = 6                                                   # num, den, sum vs, sum gm, min vs_m, max vs_m
+VSI_OPTIONS = ("c1", "c2", "c3", "alpha", "beta", "omega_0", "sigma_f", "sigma_d", "sigma_c")
+MDSI_MIN_SIDE, MDSI_MAX_SIDE = 16, 1024
+MDSI_PARTS = 3                                                  # mean re, mean im, sum of the deviations
+MDSI_OPTIONS = ("c1", "c2", "c3", "combination", "alpha", "beta", "gamma", "rho", "q", "o")
+MDSI_COMBINATIONS = ("sum", "mult")
+
+
+def vsi_kernel_size(H, W):
+    """piq's pooling kernel of vsi and mdsi: max(1, round(min(H, W) / 256)) -- Python's round, half to even: 384 -> 2, 640 -> 2,
+    641 -> 3.  The pooled map has ceil(H / k) x ceil(W / k) pixels: both metrics pad k - 1 pixels per axis before the floor pooling
+    (VSI [k // 2, (k - 1) // 2] in replicate mode, MDSI [(k - 1) // 2, k // 2] with zeros)."""
+    return max(1, round(min(H, W) / 256))
+
+
+def _number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+def vsi_check_options(c1=1.27, c2=386., c3=130., alpha=0.4, beta=0.02, omega_0=0.021, sigma_f=1.34, sigma_d=145., sigma_c=0.001):
+    """ValueError unless c1, c2, c3, omega_0, sigma_f, sigma_d, sigma_c are positive finite numbers and alpha, beta finite numbers."""
+    if not all(_number(v) and v > 0 for v in (c1, c2, c3, omega_0, sigma_f, sigma_d, sigma_c)) or not (_number(alpha) and _number(beta)):
+        raise ValueError("vsi: c1, c2, c3, omega_0, sigma_f, sigma_d, sigma_c positive numbers, alpha and beta numbers; got "
+                         f"{c1!r}, {c2!r}, {c3!r}, {omega_0!r}, {sigma_f!r}, {sigma_d!r}, {sigma_c!r}, {alpha!r}, {beta!r}")
+
+
+def mdsi_check_options(c1=140., c2=55., c3=550., combination="sum", alpha=0.6, beta=0.1, gamma=0.2, rho=1., q=0.25, o=0.25):
+    """ValueError unless combination is 'sum' or 'mult', c1, c2, c3, rho are positive finite numbers and alpha, beta, gamma, q, o
+    finite numbers."""
+    if not (isinstance(combination, str) and combination in MDSI_COMBINATIONS):
+        raise ValueError(f"mdsi: combination must be one of {MDSI_COMBINATIONS}, got {combination!r}")
+    if not all(_number(v) and v > 0 for v in (c1, c2, c3, rho)) or not all(_number(v) for v in (alpha, beta, gamma, q, o)):
+        raise ValueError("mdsi: c1, c2, c3, rho positive numbers, alpha, beta, gamma, q, o numbers; got "
+                         f"{c1!r}, {c2!r}, {c3!r}, {rho!r}, {alpha!r}, {beta!r}, {gamma!r}, {q!r}, {o!r}")
+
+
+@functools.lru_cache(maxsize=16)
+def vsi_log_gabor_table(omega_0=0.021, sigma_f=1.34):
+    """The (256, 256) float32 host table of SDSP's log-Gabor filter, zero frequency at [0, 0]: exp(-log(r / omega_0)^2 /
+    (2 sigma_f^2)) on the radius r of the frequency (in cycles per pixel, -1/2 .. 1/2 - 1/256 per axis), zero beyond r = 1/2 and
+    at the zero frequency.  float32 throughout and each element through piq's sequence of roundings, so the bytes are those of
+    piq's own table (tests/golden/vsi_mdsi_piq.npz holds their CRC-32).  Cached; do not modify the result."""
+    n = 256
+    f = ((torch.arange(n) + n // 2) % n - n // 2).float() / n                       # storage order: 0, 1/n, ..., then the negative ones
+    radius = torch.sqrt(f[:, None] ** 2 + f[None, :] ** 2)
+    radius = radius * (radius <= 0.5)                                               # (log(0) = -inf there: exp(-inf) = 0)
+    radius[0, 0] = 1
+    table = torch.exp(-torch.log(radius / omega_0) ** 2 / (2 * sigma_f ** 2))
+    table[0, 0] = 0
+    return table.contiguous()
+
+
+_vsi_device_tables = {}
+
+
+def _vsi_table(omega_0, sigma_f, device):
+    key = (omega_0, sigma_f, device.index if device.index is not None else torch.cuda.current_device())
+    got = _vsi_device_tables.get(key)
+    if got is None:
+        got = vsi_log_gabor_table(omega_0, sigma_f).to(device)
+        if len(_vsi_device_tables) >= 16:
+            _vsi_device_tables.clear()
+        _vsi_device_tables[key] = got
+    return got
+
+
+def _each_sources(name, input, target, pred, lo, hi):
+    """The shared argument checks of vsi_each / mdsi_each -> (contiguous fp32 sources, B, H, W); the same tensor twice stays the
+    same pointer."""
+    for t in (input, target, pred):
+        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
+            raise AssertionError(f"{name} expects (B,1,H,W) tensors of the same shape")
+    B, _, H, W = target.shape
+    if not (lo <= H <= hi and lo <= W <= hi):
+        raise ValueError(f"{name}: the kernels take images with sides in {lo}..{hi}, got {H}x{W}")
+    for t in (input, target, pred):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: HIP path needs CUDA tensors (no CPU fallback)")
+    srcs, kept = [], {}
+    for t in (input, target, pred):
+        if id(t) not in kept:
+            kept[id(t)] = t.contiguous().float()
+        srcs.append(kept[id(t)])
+    return srcs, B, H, W
+
+
+def vsi_each(input, target, pred, c1=1.27, c2=386., c3=130., alpha=0.4, beta=0.02, omega_0=0.021, sigma_f=1.34, sigma_d=145., sigma_c=0.001,
+             parts=False):
+    """VSI (piq's vsi, data_range 1, the grey channel three times) of every slice of (input, target, pred) against the same slice
+    of target, without a host read: a (3, B) float64 device tensor.  With parts=True also the (3, B, 6) float64 rows num = sum s
+    vs_max, den = sum vs_max, the sums of the source's pooled saliency and gradient maps, and the minimum and maximum of its
+    saliency map before it is stretched to [0, 1].  A slice's values depend neither on the batch it is in nor on the other two
+    image sets (mtd_vsi_each: fp32 LDS transforms at 256 x 256, everything else in double in a fixed order); an image set passed
+    twice (target as a source) is transformed once, and an image against itself gives exactly 1.  Sides in 16..1024, not
+    necessarily powers of two; anything else is a ValueError."""
+    import ctypes
+    vsi_check_options(c1, c2, c3, alpha, beta, omega_0, sigma_f, sigma_d, sigma_c)
+    srcs, B, H, W = _each_sources("vsi", input, target, pred, VSI_MIN_SIDE, VSI_MAX_SIDE)
+    L = _lib.lib()
+    dev = srcs[1].device
+    k = vsi_kernel_size(H, W)
+    table = _vsi_table(float(omega_0), float(sigma_f), dev)
+    out = torch.empty((3, B), dtype=torch.float64, device=dev)
+    rows = torch.empty((3, B, VSI_PARTS), dtype=torch.float64, device=dev) if parts else None
+    ws = K.workspace(L.mtd_vsi_ws_bytes(3, B, H, W, k), dev)
+    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    opts = (ctypes.c_double * 7)(c1, c2, c3, alpha, beta, sigma_d, sigma_c)
+    _lib.check(L.mtd_vsi_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, k, table.data_ptr(), opts, out.data_ptr(),
+                              rows.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_vsi_each")
+    return (out, rows) if parts else out
+
+
+def mdsi_each(input, target, pred, c1=140., c2=55., c3=550., combination="sum", alpha=0.6, beta=0.1, gamma=0.2, rho=1., q=0.25, o=0.25,
+              parts=False):
+    """MDSI (piq's mdsi, data_range 1, the grey channel three times) of every slice of (input, target, pred) against the same
+    slice of target, without a host read: a (3, B) float64 device tensor.  With parts=True also the (3, B, 3) float64 rows: the
+    means of the real and imaginary part of gcs^q and the sum of |gcs^q - mean|^rho.  All double in a fixed order (mtd_mdsi_each): a
+    slice's values depend neither on the batch it is in nor on the other two image sets, and an image against itself gives exactly
+    0 (with combination 'mult', or the default alpha).  Sides in 16..1024; anything else is a ValueError."""
+    import ctypes
+    mdsi_check_options(c1, c2, c3, combination, alpha, beta, gamma, rho, q, o)
+    srcs, B, H, W = _each_sources("mdsi", input, target, pred, MDSI_MIN_SIDE, MDSI_MAX_SIDE)
+    L = _lib.lib()
+    dev = srcs[1].device
+    k = vsi_kernel_size(H, W)
+    out = torch.empty((3, B), dtype=torch.float64, device=dev)
+    rows = torch.empty((3, B, MDSI_PARTS), dtype=torch.float64, device=dev) if parts else None
+    ws = K.workspace(L.mtd_mdsi_ws_bytes(3, B, H, W, k), dev)
+    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    opts = (ctypes.c_double * 9)(c1, c2, c3, alpha, beta, gamma, rho, q, o)
+    _lib.check(L.mtd_mdsi_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, k, opts, MDSI_COMBINATIONS.index(combination), out.data_ptr(),
+                               rows.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_mdsi_each")
+    return (out, rows) if parts else out
+
+
+def vsi_per_slice(input, target, pred, **kw):
+    """vsi_each as host numbers: a list of B (input, gt, pred) triples (the kernels' float64 scores).  One device -> host copy
+    for the batch."""
+    vals = vsi_each(input, target, pred, **kw).tolist()
+    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+
+
+def mdsi_per_slice(input, target, pred, **kw):
+    """mdsi_each as host numbers: a list of B (input, gt, pred) triples.  One device -> host copy for the batch."""
+    vals = mdsi_each(input, target, pred, **kw).tolist()
+    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+
+
+def compute_VSI(input, target, pred, data_range=1.0, **kw):
+    """piq's vsi(a, target) with its defaults (or the nine options) for a = input, target, pred: (input, gt, pred) floats, each the
+    mean over the batch of the per-image scores (reduction='mean')."""
+    if data_range != 1.0:
+        raise NotImplementedError("vsi: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
+    return tuple(vsi_each(input, target, pred, **kw).mean(dim=1).tolist())
+
+
+def compute_MDSI(input, target, pred, data_range=1.0, **kw):
+    """piq's mdsi(a, target) with its defaults (or the ten options) for a = input, target, pred: (input, gt, pred) floats, each
+    the mean over the batch of the per-image scores (reduction='mean')."""
+    if data_range != 1.0:
+        raise NotImplementedError("mdsi: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
+    return tuple(mdsi_each(input, target, pred, **kw).mean(dim=1).tolist())
 
 
 # ================================================================================================ perceptual metrics
