@@ -803,6 +803,62 @@ int mtd_kid(const float* X, int Nx, const float* Y, int Ny, int D, const int* xi
             double gamma, double coef0, int mmd_est, int want_var, int var_at_m, double* out, double* parts, void* ws,
             void* stream);
 
+/* ---- Multi-Scale Intrinsic Distance (module/piq/msid.py) and Inception Score (module/piq/isc.py) from the same (N, D) fp32
+ * feature rows -- DESIGN 3.20 -------------------------------------------------------------------------------------------------
+ * float64 arithmetic throughout; the starting vectors, temperatures and temperature tables are float64 on the device and the
+ * caller's.  k + 2 <= N <= MTD_MSID_MAX_N (msid.py:33 partitions at k + 1), 1 <= k <= 63, 2 <= m <= 32, 1 <= nv <= 4096, 1 <= nts <= 65536, D >= 1.  No
+ * floating-point atomics: two calls give the same bits.  Nothing is allocated or synchronised and nothing is read back: the two
+ * global stop conditions of the Lanczos iteration are words on the device that later launches read at entry, so the number of
+ * launches depends on (N, m) alone.  Null pointers and sizes out of range: MTD_EINVAL, nothing launched.  Every stage takes the
+ * one workspace of mtd_msid_ws_bytes and uses it from its start; nothing in it lives from one stage to the next.
+ *   mtd_msid_ws_bytes     bytes of `ws` for every call below at these sizes (the largest of: |X_j|^2 and one panel of
+ *                         mtd_msid_panel_rows(N) x N distances; the N x ceil(N / 32) bit mask and the degrees; the Lanczos
+ *                         state with V (m, N, nv); the (2, nts, nv) quadrature table); 0 = a size out of range.
+ *   mtd_msid_distances    dist (rows, N) = dd[j] - 2 X_i . X_j for row0 <= i < row0 + rows, dd[j] = |X_j|^2 (msid.py:29-32), the
+ *                         products on v_mfma_f64_16x16x4_f64.  The panel that mtd_msid_neighbours selects from.
+ *   mtd_msid_neighbours   nbr (N, k + 1) ints: per row the indices of its k + 1 smallest distances in rising (distance, index)
+ *                         order -- the row itself among them wherever it is that near (msid.py:33; the graph drops it).  The
+ *                         N x N distances are never held whole: panels of mtd_msid_panel_rows(N) rows, each selected from at
+ *                         once.  A NaN distance is never selected; -1 fills a row with fewer than k + 1 candidates.
+ *   mtd_msid_graph        the union of nbr's edges with their transposes, self dropped, all values 1 (msid.py:34-37,235-237) as
+ *                         CSR: rowptr (N + 1) ints, col (2 N (k + 1)) ints of which the first rowptr[N] are written, each row's
+ *                         columns rising.  Entries of nbr outside 0..N-1 are ignored.  A row's degree is rowptr[i + 1] - rowptr[i].
+ *   mtd_msid_lanczos      msid.py:49-135 on the Laplacian of that graph (normalized != 0: I - D^-1/2 A D^-1/2, else D - A) and
+ *                         the nv columns of start (N, nv): T (nv, m, m), and V (m, N, nv) where V is not NULL.  col_len: the
+ *                         length of col (offsets of rowptr are clamped to it, columns outside 0..N-1 are skipped).  Full
+ *                         reorthogonalisation, up to 100 further passes while any signed innerprod exceeds 1e-5, the break
+ *                         when every |beta| <= 1e-6 or the passes did not converge; rows of T and V after a break stay zero.
+ *                         (m - 2) * 306 + 8 launches and three memsets (m >= 3), of which (m - 2) * 299 return at entry when
+ *                         no extra pass is needed.
+ *   mtd_msid_quadrature   traces (2, nts): n * mean over the vectors of sum_j f(-t lambda_j) v_0j^2 (msid.py:193-199), f = exp
+ *                         then f = identity, by implicit QL per vector; zero rows of T give eigenvalue 0 with first component 0.
+ *   mtd_msid_combine      desc[t] = ((traces[0][t] - traces[1][t] / tables[0][t]) + tables[1][t]) / tables[2][t] * 1e6 with tables
+ *                         (3, nts) = exp(ts), sub, the normalisation's divisor (msid.py:218-220,242-256,289).
+ *   mtd_msid_distance     out[0] = max_t c[t] |dp[t] - dt[t]| (MTD_MSID_MAX; a NaN is handed on) or |dp - dt|_2 (MTD_MSID_L2; c
+ *                         is not read).
+ *   mtd_msid_descriptor   the stages chained: neighbours, graph, lanczos (V in the workspace), quadrature, combine.
+ *   mtd_is_ws_bytes       bytes of `ws` of mtd_inception_score; 0 = N, D or S < 1, S > 65535 or N / S < 1.
+ *   mtd_inception_score   isc.py:20-55 on logits X (N, D): out[0] = the mean, out[1] = the unbiased standard deviation (S == 1:
+ *                         nan) of out[2 + s] = exp(mean KL(p(y|x) || p(y))) over the rows of split s, s < S; a split is N / S
+ *                         consecutive rows, the remainder is dropped.  One workgroup per split. */
+#define MTD_MSID_MAX_N 32768
+enum { MTD_MSID_MAX = 0, MTD_MSID_L2 = 1 };
+size_t mtd_msid_ws_bytes(int N, int D, int k, int m, int nv, int nts);
+int mtd_msid_panel_rows(int N);
+int mtd_msid_distances(const float* X, int N, int D, int row0, int rows, double* dist, void* ws, void* stream);
+int mtd_msid_neighbours(const float* X, int N, int D, int k, int* nbr, void* ws, void* stream);
+int mtd_msid_graph(const int* nbr, int N, int k, int* rowptr, int* col, void* ws, void* stream);
+int mtd_msid_lanczos(const int* rowptr, const int* col, int col_len, int N, const double* start, int nv, int m, int normalized,
+                     double* T, double* V, void* ws, void* stream);
+int mtd_msid_quadrature(const double* T, int nv, int m, int N, const double* ts, int nts, double* traces, void* ws, void* stream);
+int mtd_msid_combine(const double* traces, const double* tables, int nts, double* desc, void* stream);
+int mtd_msid_distance(const double* dp, const double* dt, const double* c, int nts, int mode, double* out, void* stream);
+int mtd_msid_descriptor(const float* X, int N, int D, int k, int m, int nv, int normalized, const double* start, const double* ts,
+                        const double* tables, int nts, int* nbr, int* rowptr, int* col, double* T, double* traces, double* desc,
+                        void* ws, void* stream);
+size_t mtd_is_ws_bytes(int N, int D, int S);
+int mtd_inception_score(const float* X, int N, int D, int S, double* out, void* ws, void* stream);
+
 /* ---- FID's InceptionV3 feature network (module/piq/feature_extractors/fid_inception.py:134-168 and the block forwards
  * :198-316, built by metrics.py:17-31 compute_feat) -- DESIGN 3.9 --------------------------------------------------------
  * The 94 convolutions are mtd_conv_* launches; these are the other pieces.  Maps are NHWC fp32 on the caller's stream; source and

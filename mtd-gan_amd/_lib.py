@@ -312,6 +312,18 @@ def lib():
     sig("mtd_fid_distance", ci, vp, vp, vp, vp, ci, cd, ci, vp, vp, vp, vp)
     sig("mtd_kid_ws_bytes", sz, ci, ci)
     sig("mtd_kid", ci, vp, ci, vp, ci, ci, vp, vp, ci, ci, ci, cd, cd, ci, ci, ci, vp, vp, vp, vp)
+    sig("mtd_msid_ws_bytes", sz, ci, ci, ci, ci, ci, ci)
+    sig("mtd_msid_panel_rows", ci, ci)
+    sig("mtd_msid_distances", ci, vp, ci, ci, ci, ci, vp, vp, vp)
+    sig("mtd_msid_neighbours", ci, vp, ci, ci, ci, vp, vp, vp)
+    sig("mtd_msid_graph", ci, vp, ci, ci, vp, vp, vp, vp)
+    sig("mtd_msid_lanczos", ci, vp, vp, ci, ci, vp, ci, ci, ci, vp, vp, vp, vp)
+    sig("mtd_msid_quadrature", ci, vp, ci, ci, ci, vp, ci, vp, vp, vp)
+    sig("mtd_msid_combine", ci, vp, vp, ci, vp, vp)
+    sig("mtd_msid_distance", ci, vp, vp, vp, ci, ci, vp, vp)
+    sig("mtd_msid_descriptor", ci, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp)
+    sig("mtd_is_ws_bytes", sz, ci, ci, ci)
+    sig("mtd_inception_score", ci, vp, ci, ci, ci, vp, vp, vp)
     sig("mtd_resize_bilinear", ci, vp, ll, ll, ll, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp)
     sig("mtd_pool3x3", ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp)
     sig("mtd_global_avgpool", ci, vp, ci, vp, ci, ci, ci, ci, ci, vp)
@@ -391,6 +403,8 @@ EXPORTS = [
     "mtd_maxpool2x2", "mtd_patch_gram_l1_ws_bytes", "mtd_patch_gram_l1", "mtd_scaled_sums_f64",
     "mtd_fid_ws_bytes", "mtd_fid_stats", "mtd_fid_gemm", "mtd_fid_residual", "mtd_fid_distance",
     "mtd_kid_ws_bytes", "mtd_kid",
+    "mtd_msid_ws_bytes", "mtd_msid_panel_rows", "mtd_msid_distances", "mtd_msid_neighbours", "mtd_msid_graph", "mtd_msid_lanczos", "mtd_msid_quadrature",
+    "mtd_msid_combine", "mtd_msid_distance", "mtd_msid_descriptor", "mtd_is_ws_bytes", "mtd_inception_score",
     "mtd_resize_bilinear", "mtd_pool3x3", "mtd_global_avgpool",
     "mtd_image_metrics_each_ws_bytes", "mtd_image_metrics_each", "mtd_patch_gram_l1_each",
     "mtd_gray_png_rows_ws_bytes", "mtd_gray_png_rows",

@@ -250,18 +250,33 @@ def _iqa_option(model):
     return tuple(n for n in names if n in cfg)
 
 
-def _kid_option(model):
-    """`model.test_kid` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.kid_distance64's defaults); a dict ->
-    its keyword arguments (not `parts`).  It needs `model.fid_features`, whose feature rows it is computed from.  Anything
-    else: ValueError, before anything runs on the device."""
-    cfg = getattr(model, "test_kid", None)
+def _feature_metric_option(model, attr, what, call):
+    """An opt-in metric of the FID feature rows: absent or falsy -> None; True -> {} (the defaults of metrics.<call>); a dict -> its
+    keyword arguments (not `parts`).  It needs `model.fid_features`, whose feature rows it is computed from.  Anything else:
+    ValueError, before anything runs on the device."""
+    cfg = getattr(model, attr, None)
     if not cfg:
         return None
     if cfg is not True and not (isinstance(cfg, dict) and all(isinstance(k, str) for k in cfg) and "parts" not in cfg):
-        raise ValueError(f"model.test_kid: True or a dict of metrics.kid_distance64's keyword arguments (without `parts`); got {cfg!r}")
+        raise ValueError(f"model.{attr}: True or a dict of metrics.{call}'s keyword arguments (without `parts`); got {cfg!r}")
     if getattr(model, "fid_features", None) is None:
-        raise ValueError("model.test_kid needs model.fid_features: KID is computed from the feature rows of that extractor")
+        raise ValueError(f"model.{attr} needs model.fid_features: {what} is computed from the feature rows of that extractor")
     return {} if cfg is True else dict(cfg)
+
+
+def _kid_option(model):
+    """`model.test_kid` of test_MTD_GAN_Ours (metrics.kid_distance64's keyword arguments): _feature_metric_option."""
+    return _feature_metric_option(model, "test_kid", "KID", "kid_distance64")
+
+
+def _msid_option(model):
+    """`model.test_msid` of test_MTD_GAN_Ours (metrics.msid_distance64's keyword arguments): _feature_metric_option."""
+    return _feature_metric_option(model, "test_msid", "MSID", "msid_distance64")
+
+
+def _is_option(model):
+    """`model.test_is` of test_MTD_GAN_Ours (metrics.is_distance64's num_splits, distance): _feature_metric_option."""
+    return _feature_metric_option(model, "test_is", "the Inception Score", "is_distance64")
 
 
 def _haarpsi_option(model):
@@ -705,7 +720,14 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     float64 on the HIP kernels of csrc/kid.hip, returned as float32) and, with ret_var, input_kid_var / gt_kid_var / pred_kid_var;
     the three or six values cross in one device -> host copy.  The subsets are drawn from torch's global CPU generator as piq
     draws them, three calls' worth in the order input, gt, pred.  The CSV does not change.  Without the attribute (or with a
-    falsy value) nothing changes."""
+    falsy value) nothing changes.
+    `model.test_msid = True` / `model.test_is = True` (or dicts of metrics.msid_distance64's / metrics.is_distance64's keyword
+    arguments) add piq's Multi-Scale Intrinsic Distance and the distance of Inception Scores in the same way, from the
+    same feature rows (ValueError without `model.fid_features`, before anything runs): input_msid / gt_msid / pred_msid, then
+    input_is / gt_is / pred_is, behind the KID keys (metrics.compute_MSID / compute_IS: float64 on the HIP kernels of
+    csrc/msid.hip, returned as float32; three values per metric in one device -> host copy).  MSID's starting vectors are drawn
+    from numpy's global generator as piq draws them, three calls' worth in the order input, gt, pred; gt_msid is therefore not
+    0.  The CSV does not change; without the attributes nothing changes."""
     _iqa_option(model)                                   # (a bad value is refused before anything else is set up)
     _haarpsi_option(model)
     _fsim_option(model)
@@ -714,6 +736,8 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     _vsi_option(model)
     _mdsi_option(model)
     _kid_option(model)
+    _msid_option(model)
+    _is_option(model)
     stored = _StoredInput.from_model(model)
     dcm = _DcmSink.from_model(model, stored)
     png = _PngSink.from_model(model, save_dir)
@@ -744,6 +768,8 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         if opt is not None:
             opt["weights"] = opt["weights"].to(device)
     kid = _kid_option(model)
+    msid = _msid_option(model)
+    isc = _is_option(model)
     feats = ([], [], [])
     meters = {}
     rows = []
@@ -832,5 +858,9 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
             vals = torch.stack([t[j] for j in range(2) for t in triple] if with_var else list(triple)).tolist()       # three or six values, one copy
             for j, name in enumerate(("kid", "kid_var") if with_var else ("kid",)):
                 for who, v in zip(("input", "gt", "pred"), vals[3 * j:3 * j + 3]):
+                    meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+        for name, opt, compute in (("msid", msid, M.compute_MSID), ("is", isc, M.compute_IS)):
+            if opt is not None:
+                for who, v in zip(("input", "gt", "pred"), torch.stack(compute(*sets, **opt)).tolist()):       # three values, one copy
                     meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
     return {k: round(mm.global_avg, 7) for k, mm in meters.items()}

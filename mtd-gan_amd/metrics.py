@@ -27,6 +27,11 @@ iqa_metrics_per_slice and compute_MS_SSIM / compute_VIF / compute_GMSD (engine.t
 KID (module/piq/kid.py, vendored by the reference beside fid.py) from the same (N, D) feature rows as FID, in float64 on the HIP
 kernels of csrc/kid.hip (`mtd_kid`): kid_distance64 / compute_KID (engine.test_MTD_GAN_Ours under `model.test_kid`).
 
+MSID (module/piq/msid.py) and the Inception Score (module/piq/isc.py) from the same feature rows, in float64 on the HIP kernels
+of csrc/msid.hip (`mtd_msid_descriptor`, `mtd_msid_distance`, `mtd_inception_score`): msid_descriptor64 /
+msid_distance64 / compute_MSID and inception_score64 / is_distance64 / compute_IS (engine.test_MTD_GAN_Ours under
+`model.test_msid` and `model.test_is`).
+
 HaarPSI (module/piq/haarpsi.py: haarpsi with scales=3), the Haar wavelet perceptual similarity index, image by image on the HIP
 kernels of csrc/haarpsi.hip (`mtd_haarpsi_each`): haarpsi_each / haarpsi_per_slice and compute_HaarPSI
 (engine.test_MTD_GAN_Ours under `model.test_haarpsi`).
@@ -1380,6 +1385,204 @@ def compute_KID(input_feats, target_feats, pred_feats, **kw):
         r = kid_distance64(f, target_feats, **kw)
         out.append(tuple(v.float() for v in r) if isinstance(r, tuple) else r.float())
     return tuple(out)
+
+
+# ================================================================================================ MSID, IS
+MSID_NORMALIZATIONS = ("empty", "complete", "er", "none")
+MSID_MODES = ("max", "l2")                                    # MTD_MSID_MAX / MTD_MSID_L2
+MSID_MAX_N = 32768                                            # MTD_MSID_MAX_N
+MSID_EPSILON, MSID_NORMALIZATION = 1e-6, 1e6                  # msid.py:13-14
+
+
+def msid_tables(ts, n, k, normalize):
+    """What MSID needs from (ts, n, k) alone, by msid.py's own numpy expressions IN THE DTYPE `ts` ARRIVES IN (piq's default ts is
+    float32, and the rounding of exp(ts) and sub in that dtype is about 0.1 absolute in the descriptor), widened to float64
+    afterwards: (tables (3, len(ts)) = exp(ts) (msid.py:218), sub (:219), the divisor of _normalize_msid (:242-256); c (:389))."""
+    import numpy as np
+    expts = np.exp(ts)
+    sub = -ts * n / np.exp(ts)
+    if normalize == "empty":
+        div = np.full(ts.shape, n, dtype=np.float64)
+    elif normalize == "complete":
+        div = 1 + (n - 1) * np.exp(-(1 + 1 / (n - 1)) * ts)
+    elif normalize == "er":
+        xs = np.linspace(0, 1, n)
+        er_spectrum = 4 / np.sqrt(k) * xs + 1 - 2 / np.sqrt(k)
+        div = np.exp(-np.outer(ts, er_spectrum)).sum(-1) + MSID_EPSILON
+    else:
+        div = np.ones(ts.shape, dtype=np.float64)
+    c = np.exp(-2 * (ts + 1 / ts))
+    return np.stack([np.asarray(v, dtype=np.float64) for v in (expts, sub, div)]), np.asarray(c, dtype=np.float64)
+
+
+def _msid_ts(ts):
+    import numpy as np
+    if ts is None:
+        return torch.logspace(-1, 1, 256).numpy()                # msid.py:313,338
+    ts = ts.detach().cpu().numpy() if torch.is_tensor(ts) else np.asarray(ts)
+    if ts.ndim != 1 or ts.size < 1 or ts.size > 65536 or ts.dtype not in (np.float32, np.float64):
+        raise ValueError("msid: ts must be a one-dimensional float32 or float64 array of 1..65536 temperatures")
+    return ts
+
+
+def _msid_plan(n, ts, k, m, niters, rademacher, normalized_laplacian, normalize, starting_vectors):
+    """Every check of msid_descriptor64 that needs no device, and the draw: (ts as numpy, float64 (n, niters) starting vectors as a
+    CPU tensor).  ValueError before the library is touched."""
+    import numbers
+    import numpy as np
+    for name, v, lo, hi in (("k", k, 1, 63), ("m", m, 2, 32), ("niters", niters, 1, 4096)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+            raise ValueError(f"msid: {name} must be an integer in {lo}..{hi}, got {v!r}")
+    if normalize is None:
+        normalize = "none"
+    if normalize not in MSID_NORMALIZATIONS:
+        raise ValueError(f"msid: normalize must be one of {MSID_NORMALIZATIONS}, got {normalize!r}")
+    if not k + 2 <= n <= MSID_MAX_N:
+        raise ValueError(f"msid: a set of {n} rows with k = {k}: k + 2 <= N <= {MSID_MAX_N} expected (piq partitions each row's distances at k + 1)")
+    if normalize == "complete" and n < 2:
+        raise ValueError("msid: the 'complete' normalisation divides by n - 1")
+    ts = _msid_ts(ts)
+    if starting_vectors is None:
+        sv = np.random.randn(n, int(niters))                     # msid.py:69-73, numpy's global generator
+        if rademacher:
+            sv = np.sign(sv)
+        sv = torch.from_numpy(sv)
+    else:
+        sv = starting_vectors if torch.is_tensor(starting_vectors) else torch.from_numpy(np.asarray(starting_vectors))
+        if sv.dim() != 2 or tuple(sv.shape) != (n, niters) or sv.dtype != torch.float64:
+            raise ValueError(f"msid: starting_vectors must be a float64 ({n}, {niters}) array or tensor")
+    return ts, normalize, sv
+
+
+@torch.no_grad()
+def msid_descriptor64(feats, *, ts=None, k=5, m=10, niters=100, rademacher=False, normalized_laplacian=True, normalize="empty",
+                      starting_vectors=None, parts=False):
+    """piq's `_msid_descriptor` (module/piq/msid.py) of one (N, D) fp32 CUDA feature set in float64 on the HIP kernels of
+    csrc/msid.hip (mtd_msid_descriptor): the k-nearest-neighbour graph, its Laplacian, m Lanczos steps on niters
+    starting vectors at once with piq's reorthogonalisation and breaks, the quadrature, the variance reduction, the
+    normalisation, x 1e6 -- a (len(ts),) float64 device tensor.  The feature rows never leave the device and nothing is read
+    back inside the call; the starting vectors and the temperature tables go host -> device.
+
+    ts=None: piq's float32 logspace(-1, 1, 256); a float32 or float64 array is used in the dtype it arrives in, as piq does
+    (msid_tables).  When `starting_vectors` is omitted they are drawn on the host as np.random.randn(n, niters) (np.sign of it
+    under `rademacher`) from numpy's global generator, so np.random.seed(s) before the call gives what piq computes after the
+    same seed; a float64 (n, niters) array or tensor overrides the draw.  parts=True: a dict(nbr (N, k + 1) int32: each row's
+    k + 1 nearest in rising order, itself included where it is among them; rowptr (N + 1), col (2 N (k + 1), the first rowptr[N]
+    valid): the graph's CSR; T (niters, m, m); traces (2, len(ts))) comes second.
+
+    ValueError, before anything is launched: k outside 1..63, m outside 2..32, niters outside 1..4096, N outside k + 2..32768, an
+    unknown normalize, a ts or starting_vectors of the wrong shape or dtype."""
+    x = _kid_feats("msid_descriptor64", feats)
+    ts, normalize, sv = _msid_plan(x.shape[0], ts, k, m, niters, rademacher, normalized_laplacian, normalize, starting_vectors)
+    if not x.is_cuda:                                  # (after the argument checks: those need no device)
+        raise RuntimeError("msid_descriptor64: HIP path needs CUDA tensors (no CPU fallback)")
+    L = _lib.lib()
+    dev, (N, D), nts = x.device, x.shape, int(ts.shape[0])
+    tables, _ = msid_tables(ts, N, k, normalize)
+    import numpy as np
+    host = torch.from_numpy(np.concatenate([ts.astype(np.float64), tables.reshape(-1)]))
+    tab = host.to(dev, non_blocking=True)
+    start = sv.to(dev, non_blocking=True).contiguous()
+    nbr = torch.empty((N, k + 1), dtype=torch.int32, device=dev)
+    rowptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(2 * N * (k + 1), dtype=torch.int32, device=dev)
+    T = torch.empty((niters, m, m), dtype=torch.float64, device=dev)
+    traces = torch.empty((2, nts), dtype=torch.float64, device=dev)
+    desc = torch.empty(nts, dtype=torch.float64, device=dev)
+    ws = K.workspace(L.mtd_msid_ws_bytes(N, D, k, m, niters, nts), dev)
+    _lib.check(L.mtd_msid_descriptor(x.data_ptr(), N, D, k, m, niters, 1 if normalized_laplacian else 0, start.data_ptr(), tab.data_ptr(),
+                                     tab[nts:].data_ptr(), nts, nbr.data_ptr(), rowptr.data_ptr(), col.data_ptr(), T.data_ptr(), traces.data_ptr(),
+                                     desc.data_ptr(), ws.data_ptr(), K.stream_ptr()), "mtd_msid_descriptor")
+    return (desc, dict(nbr=nbr, rowptr=rowptr, col=col, T=T, traces=traces)) if parts else desc
+
+
+@torch.no_grad()
+def msid_distance64(pred_feats, target_feats, *, msid_mode="max", ts=None, k=5, m=10, niters=100, rademacher=False, normalized_laplacian=True,
+                    normalize="empty", starting_vectors=None):
+    """piq's MSID (module/piq/msid.py) of two (N, D) fp32 CUDA feature sets -- they may differ in N and in D -- as a 0-dim float64
+    device tensor: max_t c(t) |d_pred - d_targ| with c = exp(-2 (t + 1 / t)) in 'max' mode, the l2 norm of the difference in 'l2'
+    mode, of the two msid_descriptor64.  The starting vectors are drawn for the predicted set first and then for the target, as
+    piq does; `starting_vectors=(for_pred, for_targ)` overrides both draws.  Every argument of both sets is checked before
+    anything is drawn or launched."""
+    if msid_mode not in MSID_MODES:
+        raise ValueError(f"msid: msid_mode must be one of {MSID_MODES}, got {msid_mode!r}")
+    if starting_vectors is not None and not (isinstance(starting_vectors, (tuple, list)) and len(starting_vectors) == 2):
+        raise ValueError("msid: starting_vectors must be a (for_pred, for_targ) pair")
+    x, y = _kid_feats("msid_distance64", pred_feats), _kid_feats("msid_distance64", target_feats)
+    if x.device != y.device:
+        raise AssertionError("msid_distance64 expects two feature sets on one device")
+    kw = dict(ts=ts, k=k, m=m, niters=niters, rademacher=rademacher, normalized_laplacian=normalized_laplacian, normalize=normalize)
+    svs = []
+    for f, sv in zip((x, y), starting_vectors or (None, None)):      # every check, and both draws in piq's order, before the first launch
+        ts_np, _, sv = _msid_plan(f.shape[0], ts, k, m, niters, rademacher, normalized_laplacian, normalize, sv)
+        svs.append(sv)
+    if not (x.is_cuda and y.is_cuda):
+        raise RuntimeError("msid_distance64: HIP path needs CUDA tensors (no CPU fallback)")
+    dp, dt = (msid_descriptor64(f, starting_vectors=sv, **kw) for f, sv in zip((x, y), svs))
+    _, c = msid_tables(ts_np, x.shape[0], k, "none")
+    cd = torch.from_numpy(c).to(x.device, non_blocking=True)
+    out = torch.empty(1, dtype=torch.float64, device=x.device)
+    _lib.check(_lib.lib().mtd_msid_distance(dp.data_ptr(), dt.data_ptr(), cd.data_ptr(), dp.shape[0], MSID_MODES.index(msid_mode), out.data_ptr(),
+                                            K.stream_ptr()), "mtd_msid_distance")
+    return out[0]
+
+
+@torch.no_grad()
+def compute_MSID(input_feats, target_feats, pred_feats, **kw):
+    """(MSID(input, target), MSID(target, target), MSID(pred, target)) as 0-dim float32 device tensors, the mirror of compute_KID.
+    **kw: the keyword arguments of msid_distance64.  Each of the three is a call of its own and draws anew, in the order input,
+    gt, pred -- what three piq calls after one seed give; the target's descriptor is NOT shared between them (piq recomputes it
+    with fresh vectors, so MSID(target, target) is not 0)."""
+    if "parts" in kw:
+        raise ValueError("compute_MSID: `parts` belongs to msid_descriptor64")
+    return tuple(msid_distance64(f, target_feats, **kw).float() for f in (input_feats, target_feats, pred_feats))
+
+
+def _is_plan(n, num_splits):
+    import numbers
+    if isinstance(num_splits, bool) or not isinstance(num_splits, numbers.Integral) or not 1 <= num_splits <= 65535:
+        raise ValueError(f"inception score: num_splits must be an integer in 1..65535, got {num_splits!r}")
+    if n // num_splits < 1:
+        raise ValueError(f"inception score: {n} rows cannot be cut into {num_splits} splits (piq returns nan from empty slices)")
+
+
+@torch.no_grad()
+def inception_score64(feats, num_splits=10):
+    """piq's `inception_score` (module/piq/isc.py) of (N, D) fp32 CUDA rows in float64 on the HIP kernel of csrc/msid.hip
+    (mtd_inception_score; DESIGN 3.20): the rows' softmax, per split of N // num_splits consecutive rows (the remainder is dropped)
+    exp(mean KL(p(y|x) || p(y))); (mean, unbiased standard deviation) of the split scores as 0-dim float64 device tensors.  With one
+    split the standard deviation is nan, as piq's.  ValueError, before anything is launched: num_splits < 1 or N // num_splits < 1."""
+    x = _kid_feats("inception_score64", feats)
+    _is_plan(x.shape[0], num_splits)
+    if not x.is_cuda:
+        raise RuntimeError("inception_score64: HIP path needs CUDA tensors (no CPU fallback)")
+    L = _lib.lib()
+    out = torch.empty(2 + num_splits, dtype=torch.float64, device=x.device)
+    ws = K.workspace(L.mtd_is_ws_bytes(x.shape[0], x.shape[1], num_splits), x.device)
+    _lib.check(L.mtd_inception_score(x.data_ptr(), x.shape[0], x.shape[1], num_splits, out.data_ptr(), ws.data_ptr(), K.stream_ptr()), "mtd_inception_score")
+    return out[0], out[1]
+
+
+@torch.no_grad()
+def is_distance64(pred_feats, target_feats, num_splits=10, distance="l1"):
+    """piq's IS (isc.py:58-104): the l1 or l2 distance between the two sets' Inception Scores (of two scalars: |a - b| either
+    way), a 0-dim float64 device tensor."""
+    if distance not in ("l1", "l2"):
+        raise ValueError("Distance should be one of {`l1`, `l2`}")
+    x, y = _kid_feats("is_distance64", pred_feats), _kid_feats("is_distance64", target_feats)
+    _is_plan(x.shape[0], num_splits)
+    _is_plan(y.shape[0], num_splits)
+    if not (x.is_cuda and y.is_cuda):
+        raise RuntimeError("is_distance64: HIP path needs CUDA tensors (no CPU fallback)")
+    return (inception_score64(x, num_splits)[0] - inception_score64(y, num_splits)[0]).abs()
+
+
+@torch.no_grad()
+def compute_IS(input_feats, target_feats, pred_feats, **kw):
+    """(IS(input, target), IS(target, target), IS(pred, target)) as 0-dim float32 device tensors; **kw: num_splits, distance.
+    piq's inception_score expects raw InceptionV3 logits, whose softmax is p(y|x); what the rows are is the extractor's business:
+    InceptionV3Features here stops at pool3, so with it the score is that of the softmax over the 2048 pooled features."""
+    return tuple(is_distance64(f, target_feats, **kw).float() for f in (input_feats, target_feats, pred_feats))
 
 
 @torch.no_grad()
