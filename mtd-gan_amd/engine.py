@@ -5,6 +5,8 @@ of one iteration is `train_iteration` (D step with PCGrad, then G step); the ref
 synchronisations per iteration (16 `.item()` in MetricLogger.update plus 9 `if dot < 0` in PCGrad), this
 one gathers the 17 logged scalars into one device vector and copies it to the host once per iteration."""
 from . import _options
+import collections
+import functools
 import os
 
 import torch
@@ -233,21 +235,10 @@ def _l1_each(loss, pred, target):
     return torch.stack([torch.as_tensor(loss(pred[i:i + 1], target[i:i + 1]), device=pred.device).reshape(()) for i in range(B)])
 
 
-_IQA_COLUMNS = {"ms_ssim": "MS_SSIM", "vif": "VIF", "gmsd": "GMSD"}
-
-
-def _iqa_option(model):
-    """`model.test_iqa` of test_MTD_GAN_Ours: absent or falsy -> None; True -> all of metrics.IQA_METRICS; a tuple of names from
-    it -> those, in the order of metrics.IQA_METRICS whatever the tuple's.  Anything else: ValueError, before anything runs on the device."""
-    cfg = getattr(model, "test_iqa", None)
-    names = ("ms_ssim", "vif", "gmsd")
-    if not cfg:
-        return None
-    if cfg is True:
-        return names
-    if not isinstance(cfg, (tuple, list)) or any(n not in names for n in cfg) or len(set(cfg)) != len(cfg):
-        raise ValueError(f"model.test_iqa: True or a tuple of names from {names}; got {cfg!r}")
-    return tuple(n for n in names if n in cfg)
+def _update_triple(meters, name, triple):
+    """One sample's (input, gt, pred) values into the meters {input,gt,pred}_<name>, made in that order where they are new."""
+    for who, v in zip(("input", "gt", "pred"), triple):
+        meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
 
 
 def _feature_metric_option(model, attr, what, call):
@@ -279,162 +270,134 @@ def _is_option(model):
     return _feature_metric_option(model, "test_is", "the Inception Score", "is_distance64")
 
 
-def _haarpsi_option(model):
-    """`model.test_haarpsi` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.haarpsi_each's defaults); a
-    dict with keys from c, alpha (positive numbers) and subsample (a bool) -> those keyword arguments.  Anything else: ValueError,
-    before anything runs on the device."""
-    cfg = getattr(model, "test_haarpsi", None)
-    if not cfg:
-        return None
-    if cfg is True:
-        return {}
-    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0          # noqa: E731
-    if (not isinstance(cfg, dict) or set(cfg) - {"c", "alpha", "subsample"} or not all(number(cfg[k]) for k in ("c", "alpha") if k in cfg)
-            or not isinstance(cfg.get("subsample", True), bool)):
-        raise ValueError(f"model.test_haarpsi: True or a dict with the keys c, alpha (positive numbers), subsample (a bool); got {cfg!r}")
-    return dict(cfg)
+# ---------------------------------------------------------------------- the opt-in per-slice metrics of test_MTD_GAN_Ours
+# One entry of _PER_SLICE per metric; the table's order is the order of the meter keys, the CSV columns and the blocks of the
+# per-slice host read.
+#   attr     the `model.test_*` attribute that switches the metric on
+#   parse    parse(model, entry) -> the keyword arguments of `each`, or None where the attribute is absent or off; ValueError for
+#            any other value, before anything runs on the device
+#   each     the name of metrics.<each>(input, target, pred, **keywords) -> a (3, B) float64 device tensor, rows input, gt, pred
+#            (looked up when used: metrics is imported lazily) -- or (names, 3, B) with several result names, of which the
+#            keyword `which` holds those chosen
+#   columns  result name -> CSV column label; the meters are {input,gt,pred}_<name>
+#   text     the entry's part of parse's error message
+# Two keyword names are the loop's own, so no `each` may use them for anything else: `which` (a tuple of result names: the names
+# chosen of an entry with several, _names) and `weights` (a tensor the loop moves to the device once, _test_loop).
+_PerSlice = collections.namedtuple("_PerSlice", "attr parse each columns text")
 
 
-def _haarpsi_update(triple, meters):
-    """The HaarPSI meters of one sample (after the sample's other keys); returns its CSV cell, the pred value."""
-    for who, v in zip(("input", "gt", "pred"), triple):
-        meters.setdefault(f"{who}_haarpsi", _Meter()).update(v, 1)
-    return (triple[2],)
-
-
-def _fsim_option(model):
-    """`model.test_fsim` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.fsim_each's defaults); a dict with keys
-    from scales, orientations, min_length, mult, sigma_f, delta_theta, k that metrics.fsim_check_options accepts -> those keyword
-    arguments.  Anything else: ValueError, before anything runs on the device."""
+def _iqa_parse(model, e):
+    """absent or falsy -> None; True -> all of metrics.IQA_METRICS; a tuple of names from it -> those, in the order of
+    metrics.IQA_METRICS whatever the tuple's."""
     from . import metrics as M
-    cfg = getattr(model, "test_fsim", None)
+    cfg = getattr(model, e.attr, None)
     if not cfg:
         return None
-    if cfg is True:
-        return {}
     try:
-        if not isinstance(cfg, dict) or set(cfg) - set(M.FSIM_OPTIONS):
-            raise ValueError("not a dict of the options")
-        M.fsim_check_options(**cfg)
-    except ValueError as e:
-        raise ValueError("model.test_fsim: True or a dict with the keys scales (1..4), orientations (1..8), min_length, mult, sigma_f, "
-                         f"delta_theta (positive numbers, sigma_f not 1), k (a number); got {cfg!r} ({e})") from None
-    return dict(cfg)
+        if cfg is not True and not isinstance(cfg, (tuple, list)):
+            raise ValueError("not a tuple")
+        return dict(which=M.IQA_METRICS if cfg is True else M._iqa_which(cfg))
+    except ValueError:
+        raise ValueError(f"model.{e.attr}: {e.text} {M.IQA_METRICS}; got {cfg!r}") from None
 
 
-def _fsim_update(triple, meters):
-    """The FSIM meters of one sample (after the sample's other keys); returns its CSV cell, the pred value."""
-    for who, v in zip(("input", "gt", "pred"), triple):
-        meters.setdefault(f"{who}_fsim", _Meter()).update(v, 1)
-    return (triple[2],)
-
-
-def _vsi_option(model):
-    """`model.test_vsi` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.vsi_each's defaults); a dict with keys
-    from c1, c2, c3, alpha, beta, omega_0, sigma_f, sigma_d, sigma_c that metrics.vsi_check_options accepts -> those keyword
-    arguments.  Anything else: ValueError, before anything runs on the device."""
+def _checked_parse(model, e):
+    """absent or falsy -> None; True -> {} (the defaults of metrics.X_each); a dict with keys from metrics.X_OPTIONS that
+    metrics.X_check_options accepts -> those keyword arguments (X: `each` without its `_each`)."""
     from . import metrics as M
-    cfg = getattr(model, "test_vsi", None)
+    cfg = getattr(model, e.attr, None)
     if not cfg:
         return None
     if cfg is True:
         return {}
+    stem = e.each[:-len("_each")]
     try:
-        if not isinstance(cfg, dict) or set(cfg) - set(M.VSI_OPTIONS):
+        if not isinstance(cfg, dict) or set(cfg) - set(getattr(M, f"{stem.upper()}_OPTIONS")):
             raise ValueError("not a dict of the options")
-        M.vsi_check_options(**cfg)
-    except ValueError as e:
-        raise ValueError("model.test_vsi: True or a dict with the keys c1, c2, c3, omega_0, sigma_f, sigma_d, sigma_c (positive numbers), "
-                         f"alpha, beta (numbers); got {cfg!r} ({e})") from None
+        getattr(M, f"{stem}_check_options")(**cfg)
+    except ValueError as err:
+        raise ValueError(f"model.{e.attr}: True or a dict with the keys {e.text}; got {cfg!r} ({err})") from None
     return dict(cfg)
 
 
-def _mdsi_option(model):
-    """`model.test_mdsi` of test_MTD_GAN_Ours: absent or falsy -> None; True -> {} (metrics.mdsi_each's defaults); a dict with keys
-    from c1, c2, c3, combination, alpha, beta, gamma, rho, q, o that metrics.mdsi_check_options accepts -> those keyword arguments.
-    Anything else: ValueError, before anything runs on the device."""
+def _vgg16_parse(model, e, form=lambda e, cfg: (cfg, {})):
+    """A metric on `model.perceptual_vgg16` with weights of the caller's: absent, None, False or empty -> None; the weights in a
+    form metrics.X_weights takes -> the keyword arguments vgg and weights (the float64 table).  form(entry, value) -> (weights,
+    further keyword arguments) opens a wrapped value."""
     from . import metrics as M
-    cfg = getattr(model, "test_mdsi", None)
-    if not cfg:
-        return None
-    if cfg is True:
-        return {}
-    try:
-        if not isinstance(cfg, dict) or set(cfg) - set(M.MDSI_OPTIONS):
-            raise ValueError("not a dict of the options")
-        M.mdsi_check_options(**cfg)
-    except ValueError as e:
-        raise ValueError("model.test_mdsi: True or a dict with the keys c1, c2, c3, rho (positive numbers), combination ('sum' or 'mult'), "
-                         f"alpha, beta, gamma, q, o (numbers); got {cfg!r} ({e})") from None
-    return dict(cfg)
-
-
-def _lpips_option(model):
-    """`model.test_lpips` of test_MTD_GAN_Ours: absent or falsy -> None; LPIPS's linear-layer weights in a form
-    metrics.lpips_weights takes (five tensors, or a path), or `dict(weights=..., distance="mse" | "mae")` -> the keyword arguments
-    of metrics.lpips_each (vgg, weights as the float64 table, distance).  It needs `model.perceptual_vgg16`, a
-    metrics.VGG16Features.  Anything else: ValueError, before anything runs on the device."""
-    from . import metrics as M
-    cfg = getattr(model, "test_lpips", None)
+    cfg = getattr(model, e.attr, None)
     if cfg is None or cfg is False or (isinstance(cfg, (dict, list, tuple, str)) and not cfg):
         return None
+    cfg, more = form(e, cfg)
+    if cfg is True:
+        raise ValueError(f"model.{e.attr}: no weights ship with this package; pass {e.text}")
+    try:
+        table = getattr(M, e.each[:-len("_each")] + "_weights")(cfg)
+    except (ValueError, OSError) as err:
+        raise ValueError(f"model.{e.attr}: {err}") from None
+    vgg = getattr(model, "perceptual_vgg16", None)
+    if not isinstance(vgg, M.VGG16Features):
+        label, = e.columns.values()
+        raise ValueError(f"model.{e.attr} needs model.perceptual_vgg16 = metrics.VGG16Features(state_dict): {label} is computed on its maps")
+    return dict(vgg=vgg, weights=table, **more)
+
+
+def _lpips_form(e, cfg):
+    """`model.test_lpips`: the weights, or `dict(weights=..., distance="mse" | "mae")` -> (weights, dict(distance=...))."""
+    from . import metrics as M
     distance = "mse"
     if isinstance(cfg, dict):
         if set(cfg) - {"weights", "distance"} or "weights" not in cfg:
-            raise ValueError(f"model.test_lpips: the weights, or a dict with the keys weights and distance; got the keys {sorted(cfg)}")
+            raise ValueError(f"model.{e.attr}: the weights, or a dict with the keys weights and distance; got the keys {sorted(cfg)}")
         cfg, distance = cfg["weights"], cfg.get("distance", "mse")
     if distance not in M.LPIPS_DISTANCES:
-        raise ValueError(f"model.test_lpips: distance must be one of {M.LPIPS_DISTANCES}, got {distance!r}")
-    if cfg is True:
-        raise ValueError("model.test_lpips: no weights ship with this package; pass LPIPS's five linear-layer weight tensors or a path to them")
-    try:
-        table = M.lpips_weights(cfg)
-    except (ValueError, OSError) as e:
-        raise ValueError(f"model.test_lpips: {e}") from None
-    vgg = getattr(model, "perceptual_vgg16", None)
-    if not isinstance(vgg, M.VGG16Features):
-        raise ValueError("model.test_lpips needs model.perceptual_vgg16 = metrics.VGG16Features(state_dict): LPIPS is computed on its maps")
-    return dict(vgg=vgg, weights=table, distance=distance)
+        raise ValueError(f"model.{e.attr}: distance must be one of {M.LPIPS_DISTANCES}, got {distance!r}")
+    return cfg, dict(distance=distance)
 
 
-def _dists_option(model):
-    """`model.test_dists` of test_MTD_GAN_Ours: absent or falsy -> None; DISTS's alpha / beta in a form metrics.dists_weights takes
-    (a dict with `alpha` and `beta`, or a path) -> the keyword arguments of metrics.dists_each (vgg, weights as the float64
-    table).  It needs `model.perceptual_vgg16`.  Anything else: ValueError, before anything runs on the device."""
-    from . import metrics as M
-    cfg = getattr(model, "test_dists", None)
-    if cfg is None or cfg is False or (isinstance(cfg, (dict, list, tuple, str)) and not cfg):
-        return None
-    if cfg is True:
-        raise ValueError("model.test_dists: no weights ship with this package; pass DISTS's dict of alpha and beta or a path to it")
-    try:
-        table = M.dists_weights(cfg)
-    except (ValueError, OSError) as e:
-        raise ValueError(f"model.test_dists: {e}") from None
-    vgg = getattr(model, "perceptual_vgg16", None)
-    if not isinstance(vgg, M.VGG16Features):
-        raise ValueError("model.test_dists needs model.perceptual_vgg16 = metrics.VGG16Features(state_dict): DISTS is computed on its maps")
-    return dict(vgg=vgg, weights=table)
+_PER_SLICE = (
+    _PerSlice("test_iqa", _iqa_parse, "iqa_metrics_each", {"ms_ssim": "MS_SSIM", "vif": "VIF", "gmsd": "GMSD"}, "True or a tuple of names from"),
+    _PerSlice("test_haarpsi", _checked_parse, "haarpsi_each", {"haarpsi": "HaarPSI"}, "c, alpha (positive numbers), subsample (a bool)"),
+    _PerSlice("test_fsim", _checked_parse, "fsim_each", {"fsim": "FSIM"},
+              "scales (1..4), orientations (1..8), min_length, mult, sigma_f, delta_theta (positive numbers, sigma_f not 1), k (a number)"),
+    _PerSlice("test_lpips", functools.partial(_vgg16_parse, form=_lpips_form), "lpips_each", {"lpips": "LPIPS"}, "LPIPS's five linear-layer weight tensors or a path to them"),
+    _PerSlice("test_dists", _vgg16_parse, "dists_each", {"dists": "DISTS"}, "DISTS's dict of alpha and beta or a path to it"),
+    _PerSlice("test_vsi", _checked_parse, "vsi_each", {"vsi": "VSI"},
+              "c1, c2, c3, omega_0, sigma_f, sigma_d, sigma_c (positive numbers), alpha, beta (numbers)"),
+    _PerSlice("test_mdsi", _checked_parse, "mdsi_each", {"mdsi": "MDSI"},
+              "c1, c2, c3, rho (positive numbers), combination ('sum' or 'mult'), alpha, beta, gamma, q, o (numbers)"),
+)
 
 
-def _named_update(name, triple, meters):
-    """The {input,gt,pred}_<name> meters of one sample (after the sample's other keys); returns its CSV cell, the pred value."""
-    for who, v in zip(("input", "gt", "pred"), triple):
-        meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
-    return (triple[2],)
+def _per_slice_options(model):
+    """The (entry, keyword arguments) pairs of the entries of _PER_SLICE that the model switches on, in the table's order."""
+    return [(e, kw) for e in _PER_SLICE for kw in (e.parse(model, e),) if kw is not None]
 
 
-def _iqa_update(iqa, triples, meters):
-    """The meters of one sample (after the sample's other keys); returns its CSV cells, the pred values."""
-    for name, triple in zip(iqa, triples):
-        for who, v in zip(("input", "gt", "pred"), triple):
-            meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
-    return tuple(t[2] for t in triples)
+def _names(e, kw):
+    """The result names of an active entry: those chosen by `which`, or the entry's one."""
+    return kw.get("which", tuple(e.columns))
 
 
-def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa=None, haarpsi=None, fsim=None, lpips=None,
-                          dists=None, vsi=None, mdsi=None):
-    """One loader batch of test_MTD_GAN_Ours under `model.test_per_slice`: B meter updates and B rows from one host read."""
+def _table_option(attr, model):
+    """One attribute's parse alone: `model.<attr>` -> the keyword arguments or None."""
+    e, = (e for e in _PER_SLICE if e.attr == attr)
+    return e.parse(model, e)
+
+
+_haarpsi_option, _fsim_option, _lpips_option, _dists_option, _vsi_option, _mdsi_option = (
+    functools.partial(_table_option, attr) for attr in ("test_haarpsi", "test_fsim", "test_lpips", "test_dists", "test_vsi", "test_mdsi"))
+
+
+def _iqa_option(model):
+    """`model.test_iqa` as the tuple of chosen names, or None."""
+    kw = _table_option("test_iqa", model)
+    return kw and kw["which"]
+
+
+def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, active=()):
+    """One loader batch of test_MTD_GAN_Ours under `model.test_per_slice`: B meter updates and B rows from one host read.
+    active: _per_slice_options' pairs."""
     from . import kernels as K, metrics as M
     B, _, H, W = x.shape
     clipped = K.clip01(pred.contiguous())
@@ -444,57 +407,31 @@ def _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats
     if fid_features is not None:
         for rows_, f in zip(feats, M.compute_feat(x, y, clipped, extractor=fid_features)):
             rows_.append(f.float())
-    if iqa is not None:
-        parts.append(M.iqa_metrics_each(x, y, clipped, iqa).flatten())          # (metric, who, slice) float64, behind the others
-    if haarpsi is not None:
-        parts.append(M.haarpsi_each(x, y, clipped, **haarpsi).flatten())        # (who, slice) float64, behind the iqa block
-    if fsim is not None:
-        parts.append(M.fsim_each(x, y, clipped, **fsim).flatten())              # (who, slice) float64, behind the HaarPSI block
-    if lpips is not None:
-        parts.append(M.lpips_each(x, y, clipped, **lpips).flatten())            # (who, slice) float64, behind the FSIM block
-    if dists is not None:
-        parts.append(M.dists_each(x, y, clipped, **dists).flatten())            # (who, slice) float64, behind the LPIPS block
-    if vsi is not None:
-        parts.append(M.vsi_each(x, y, clipped, **vsi).flatten())                # (who, slice) float64, behind the DISTS block
-    if mdsi is not None:
-        parts.append(M.mdsi_each(x, y, clipped, **mdsi).flatten())              # (who, slice) float64, behind the VSI block
+    for e, kw in active:                              # (name, who, slice) float64 each, behind the others in the table's order
+        parts.append(getattr(M, e.each)(x, y, clipped, **kw).flatten())
     vals = torch.cat(parts).tolist()                  # every per-slice value of the batch in one device -> host copy
     l1 = vals[:B]
     sums = [[vals[B + (k * B + i) * 2:B + (k * B + i) * 2 + 2] for i in range(B)] for k in range(3)]
     six = [vals[7 * B + r * B:7 * B + (r + 1) * B] for r in range(6)] if vgg is not None else None
     pm = M._slice_triples(sums, H * W)
-    q0 = (13 if vgg is not None else 7) * B           # where the iqa block starts
-    q1 = q0 + 3 * B * len(iqa or ())                  # where the HaarPSI block starts
-    q2 = q1 + (3 * B if haarpsi is not None else 0)   # where the FSIM block starts
-    q3 = q2 + (3 * B if fsim is not None else 0)      # where the LPIPS block starts
-    q4 = q3 + (3 * B if lpips is not None else 0)     # where the DISTS block starts
-    q5 = q4 + (3 * B if dists is not None else 0)     # where the VSI block starts
-    q6 = q5 + (3 * B if vsi is not None else 0)       # where the MDSI block starts
     paths = batch_data.get("path_n_20") if isinstance(batch_data, dict) else None
     for i in range(B):
         meters.setdefault("L1_loss", _Meter()).update(l1[i], 1)
         perceptual = ()
         if six is not None:
             for j, name in enumerate(("pl", "tml")):
-                for k, who in enumerate(("input", "gt", "pred")):
-                    meters.setdefault(f"{who}_{name}", _Meter()).update(six[3 * j + k][i], 1)
+                _update_triple(meters, name, [six[3 * j + k][i] for k in range(3)])
             perceptual = (six[2][i], six[5][i])
         for name in ("rmse", "psnr", "ssim"):
-            for who, v in zip(("input", "gt", "pred"), pm[name][i]):
-                meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
-        more = _iqa_update(iqa, [tuple(vals[q0 + (r * 3 + k) * B + i] for k in range(3)) for r in range(len(iqa))], meters) if iqa is not None else ()
-        if haarpsi is not None:
-            more += _haarpsi_update(tuple(vals[q1 + k * B + i] for k in range(3)), meters)
-        if fsim is not None:
-            more += _fsim_update(tuple(vals[q2 + k * B + i] for k in range(3)), meters)
-        if lpips is not None:
-            more += _named_update("lpips", tuple(vals[q3 + k * B + i] for k in range(3)), meters)
-        if dists is not None:
-            more += _named_update("dists", tuple(vals[q4 + k * B + i] for k in range(3)), meters)
-        if vsi is not None:
-            more += _named_update("vsi", tuple(vals[q5 + k * B + i] for k in range(3)), meters)
-        if mdsi is not None:
-            more += _named_update("mdsi", tuple(vals[q6 + k * B + i] for k in range(3)), meters)
+            _update_triple(meters, name, pm[name][i])
+        more = ()
+        q = (13 if vgg is not None else 7) * B        # where the table's blocks start: each name's is 3 B values, who-major
+        for e, kw in active:
+            for name in _names(e, kw):
+                triple = vals[q + i:q + 3 * B:B]
+                _update_triple(meters, name, triple)
+                more += (triple[2],)
+                q += 3 * B
         path = paths[i] if paths is not None else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][i][2], pm["psnr"][i][2], pm["ssim"][i][2]) + more)
 
@@ -728,48 +665,32 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     csrc/msid.hip, returned as float32; three values per metric in one device -> host copy).  MSID's starting vectors are drawn
     from numpy's global generator as piq draws them, three calls' worth in the order input, gt, pred; gt_msid is therefore not
     0.  The CSV does not change; without the attributes nothing changes."""
-    _iqa_option(model)                                   # (a bad value is refused before anything else is set up)
-    _haarpsi_option(model)
-    _fsim_option(model)
-    _lpips_option(model)
-    _dists_option(model)
-    _vsi_option(model)
-    _mdsi_option(model)
-    _kid_option(model)
-    _msid_option(model)
-    _is_option(model)
+    active = _per_slice_options(model)                   # (a bad value is refused before anything else is set up)
+    after = (_kid_option(model), _msid_option(model), _is_option(model))
     stored = _StoredInput.from_model(model)
     dcm = _DcmSink.from_model(model, stored)
     png = _PngSink.from_model(model, save_dir)
     if png is None:
-        return _test_loop(model, loss, data_loader, device, save_dir, None, stored, dcm)
+        return _test_loop(model, loss, data_loader, device, save_dir, None, stored, dcm, active, after)
     try:
-        return _test_loop(model, loss, data_loader, device, save_dir, png, stored, dcm)
+        return _test_loop(model, loss, data_loader, device, save_dir, png, stored, dcm, active, after)
     finally:
         png.writer.close()
 
 
-def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm=None):
+def _test_loop(model, loss, data_loader, device, save_dir, png, stored, dcm, active, after):
     """The body of test_MTD_GAN_Ours; png: the _PngSink of `model.test_save_png`, stored: the _StoredInput of
-    `model.test_from_stored`, dcm: the _DcmSink of `model.test_save_dcm`, or None each."""
+    `model.test_from_stored`, dcm: the _DcmSink of `model.test_save_dcm`, or None each; active: _per_slice_options' pairs;
+    after: the parsed options of the metrics of the feature rows (kid, msid, is), None where off."""
     from . import metrics as M
     model.Generator.eval()
     vgg = getattr(model, "perceptual_vgg", None)
     fid_features = getattr(model, "fid_features", None)
     per_slice = bool(getattr(model, "test_per_slice", False))
-    iqa = _iqa_option(model)
-    haarpsi = _haarpsi_option(model)
-    fsim = _fsim_option(model)
-    lpips = _lpips_option(model)
-    dists = _dists_option(model)
-    vsi = _vsi_option(model)
-    mdsi = _mdsi_option(model)
-    for opt in (lpips, dists):                           # the small weight tables go to the device once, not once per batch
-        if opt is not None:
-            opt["weights"] = opt["weights"].to(device)
-    kid = _kid_option(model)
-    msid = _msid_option(model)
-    isc = _is_option(model)
+    for _, kw in active:                                 # the small weight tables go to the device once, not once per batch
+        if "weights" in kw:
+            kw["weights"] = kw["weights"].to(device)
+    kid, msid, isc = after
     feats = ([], [], [])
     meters = {}
     rows = []
@@ -793,7 +714,7 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         if dcm is not None:
             slices = dcm.begin(pred, words, table)             # likewise
         if per_slice:
-            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, iqa, haarpsi, fsim, lpips, dists, vsi, mdsi)
+            _test_batch_per_slice(loss, batch_data, x, y, pred, vgg, fid_features, feats, meters, rows, active)
             if png is not None:
                 png.submit(images, batch_data, k0)
             if dcm is not None:
@@ -806,31 +727,20 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         if vgg is not None:
             six = M.perceptual_metrics(x, y, clipped, vgg).tolist()        # the slice's six values in one device -> host copy
             for j, name in enumerate(("pl", "tml")):
-                for who, v in zip(("input", "gt", "pred"), six[3 * j:3 * j + 3]):
-                    meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+                _update_triple(meters, name, six[3 * j:3 * j + 3])
             perceptual = (six[2], six[5])
         if fid_features is not None:
             for rows_, f in zip(feats, M.compute_feat(x, y, clipped, extractor=fid_features)):
                 rows_.append(f.float())
         pm = M.pixel_metrics(x, y, clipped)
         for name, triple in pm.items():
-            for who, v in zip(("input", "gt", "pred"), triple):
-                meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+            _update_triple(meters, name, triple)
         more = ()
-        if iqa is not None:          # the batch is one sample: the mean over its slices, piq's reduction='mean' (one more host read)
-            more = _iqa_update(iqa, M.iqa_metrics_each(x, y, clipped, iqa).mean(dim=2).tolist(), meters)
-        if haarpsi is not None:      # likewise
-            more += _haarpsi_update(tuple(M.haarpsi_each(x, y, clipped, **haarpsi).mean(dim=1).tolist()), meters)
-        if fsim is not None:         # likewise
-            more += _fsim_update(tuple(M.fsim_each(x, y, clipped, **fsim).mean(dim=1).tolist()), meters)
-        if lpips is not None:        # likewise
-            more += _named_update("lpips", tuple(M.lpips_each(x, y, clipped, **lpips).mean(dim=1).tolist()), meters)
-        if dists is not None:        # likewise
-            more += _named_update("dists", tuple(M.dists_each(x, y, clipped, **dists).mean(dim=1).tolist()), meters)
-        if vsi is not None:          # likewise
-            more += _named_update("vsi", tuple(M.vsi_each(x, y, clipped, **vsi).mean(dim=1).tolist()), meters)
-        if mdsi is not None:         # likewise
-            more += _named_update("mdsi", tuple(M.mdsi_each(x, y, clipped, **mdsi).mean(dim=1).tolist()), meters)
+        for e, kw in active:         # the batch is one sample: the mean over its slices, piq's reduction='mean' (one more host read each)
+            means = getattr(M, e.each)(x, y, clipped, **kw).mean(dim=-1).reshape(-1, 3).tolist()
+            for name, triple in zip(_names(e, kw), means):
+                _update_triple(meters, name, triple)
+                more += (triple[2],)
         path = batch_data.get("path_n_20", [f"slice_{len(rows)}"])[0] if isinstance(batch_data, dict) else f"slice_{len(rows)}"
         rows.append((path,) + perceptual + (pm["rmse"][2], pm["psnr"][2], pm["ssim"][2]) + more)
         if png is not None:
@@ -842,25 +752,19 @@ def _test_loop(model, loss, data_loader, device, save_dir, png, stored=None, dcm
         os.makedirs(save_dir, exist_ok=True)
         with open(os.path.join(save_dir, "pred_results.csv"), "w") as f:
             f.write((",PATH,PL,TML,RMSE,PSNR,SSIM" if vgg is not None else ",PATH,RMSE,PSNR,SSIM")
-                    + "".join("," + _IQA_COLUMNS[n] for n in iqa or ()) + (",HaarPSI" if haarpsi is not None else "") + (",FSIM" if fsim is not None else "")
-                    + (",LPIPS" if lpips is not None else "") + (",DISTS" if dists is not None else "")
-                    + (",VSI" if vsi is not None else "") + (",MDSI" if mdsi is not None else "") + "\n")
+                    + "".join("," + e.columns[name] for e, kw in active for name in _names(e, kw)) + "\n")
             for i, r in enumerate(rows):
                 f.write(f"{i}," + ",".join(str(v) for v in r) + "\n")
     if fid_features is not None:
         sets = [torch.cat(f, dim=0) for f in feats]
-        fid = torch.stack(M.compute_FID(*sets)).tolist()       # the three values in one device -> host copy
-        for who, v in zip(("input", "gt", "pred"), fid):
-            meters.setdefault(f"{who}_fid", _Meter()).update(v, 1)
+        _update_triple(meters, "fid", torch.stack(M.compute_FID(*sets)).tolist())       # the three values in one device -> host copy
         if kid is not None:
             triple = M.compute_KID(*sets, **kid)
             with_var = bool(kid.get("ret_var"))
             vals = torch.stack([t[j] for j in range(2) for t in triple] if with_var else list(triple)).tolist()       # three or six values, one copy
             for j, name in enumerate(("kid", "kid_var") if with_var else ("kid",)):
-                for who, v in zip(("input", "gt", "pred"), vals[3 * j:3 * j + 3]):
-                    meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+                _update_triple(meters, name, vals[3 * j:3 * j + 3])
         for name, opt, compute in (("msid", msid, M.compute_MSID), ("is", isc, M.compute_IS)):
             if opt is not None:
-                for who, v in zip(("input", "gt", "pred"), torch.stack(compute(*sets, **opt)).tolist()):       # three values, one copy
-                    meters.setdefault(f"{who}_{name}", _Meter()).update(v, 1)
+                _update_triple(meters, name, torch.stack(compute(*sets, **opt)).tolist())       # three values, one copy
     return {k: round(mm.global_avg, 7) for k, mm in meters.items()}

@@ -127,19 +127,70 @@ def pixel_metrics(input, target, pred):
     return {k: tuple(v) for k, v in out.items()}
 
 
+# The shared pieces of the image-by-image metrics below (the *_each functions on (input, target, pred)).  Each function calls the
+# checks where its own refusals stand, so which error a doubly wrong call meets first is the function's choice, not the helpers'.
+def _image_shape(what, input, target, pred):
+    """(B, H, W) of three (B,1,H,W) tensors of one shape; AssertionError otherwise (`what`: the message's subject and verb)."""
+    for t in (input, target, pred):
+        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
+            raise AssertionError(f"{what} (B,1,H,W) tensors of the same shape")
+    return target.shape[0], target.shape[2], target.shape[3]
+
+
+def _need_cuda(name, input, target, pred):
+    for t in (input, target, pred):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: HIP path needs CUDA tensors (no CPU fallback)")
+
+
+def _fp32_sources(input, target, pred):
+    """The three as contiguous fp32 tensors; the same tensor twice stays the same pointer (a kernel that transforms its sources
+    then transforms it once)."""
+    kept = {}
+    for t in (input, target, pred):
+        if id(t) not in kept:
+            kept[id(t)] = t.contiguous().float()
+    return [kept[id(t)] for t in (input, target, pred)]
+
+
+def _number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+def _who_triples(vals):
+    """A (3, B) tensor as nested lists -> the list of B (input, gt, pred) triples."""
+    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+
+
+def _batch_means(name, data_range, each, *args, **kw):
+    """The body of the compute_* wrappers: the data_range guard, then the three means over the batch of each(*args, **kw) -- a
+    (3, B) tensor, or IQA's (1, 3, B) -- as a (3,) device tensor."""
+    if data_range != 1.0:
+        raise NotImplementedError(f"{name}: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
+    return each(*args, **kw).reshape(3, -1).mean(dim=1)
+
+
+def _device_cached(cache, key, device, build):
+    """build()'s device tensors, kept per (key, device index) in `cache`: 16 entries, cleared when full."""
+    key += (device.index if device.index is not None else torch.cuda.current_device(),)
+    got = cache.get(key)
+    if got is None:
+        got = build()
+        if len(cache) >= 16:
+            cache.clear()
+        cache[key] = got
+    return got
+
+
 def pixel_metrics_each(input, target, pred, clip_pred=False):
     """The sums of pixel_metrics image by image, without a host read: a (3, B, 2) float64 device tensor, [k][i] = (sum of squared
     error, sum of the SSIM map) of slice i of (input, target, pred)[k] against slice i of target -- the bits of a one-slice
     mtd_image_metrics call (mtd_image_metrics_each: two launches for the three pairs of the batch).  `clip_pred`: clip the
     prediction to [0, 1] on the way in."""
-    for t in (input, target, pred):
-        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
-            raise AssertionError("pixel metrics expect (B,1,H,W) tensors of the same shape")
-        if not t.is_cuda:
-            raise RuntimeError("pixel metrics: HIP path needs CUDA tensors (no CPU fallback)")
+    B, H, W = _image_shape("pixel metrics expect", input, target, pred)
+    _need_cuda("pixel metrics", input, target, pred)
     import ctypes
-    srcs = [t.contiguous().float() for t in (input, target, pred)]
-    B, _, H, W = srcs[1].shape
+    srcs = _fp32_sources(input, target, pred)
     L = _lib.lib()
     out = torch.empty((3, B, 2), dtype=torch.float64, device=srcs[1].device)
     ws = K.workspace(L.mtd_image_metrics_each_ws_bytes(3, B, H, W), out.device)
@@ -191,19 +242,15 @@ def iqa_metrics_each(input, target, pred, which=IQA_METRICS, sigma_n_sq=2.0, par
     [0, 255], so its default 2.0 is taken as it stands; pass 2 / 255**2 for the convention of the original [0, 255] code.
     MS-SSIM needs sides of at least 161, VIFp of at least 41, GMSD of at least 2 (ValueError, as piq raises)."""
     which = _iqa_which(which)
-    for t in (input, target, pred):
-        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
-            raise AssertionError("iqa metrics expect (B,1,H,W) tensors of the same shape")
-        if not t.is_cuda:
-            raise RuntimeError("iqa metrics: HIP path needs CUDA tensors (no CPU fallback)")
-    B, _, H, W = target.shape
+    B, H, W = _image_shape("iqa metrics expect", input, target, pred)
+    _need_cuda("iqa metrics", input, target, pred)
     for n in which:
         if H < IQA_MIN_SIDE[n] or W < IQA_MIN_SIDE[n]:
             raise ValueError(f"iqa metrics: {n} needs images of at least {IQA_MIN_SIDE[n]}x{IQA_MIN_SIDE[n]}, got {H}x{W}")
     if not sigma_n_sq > 0:
         raise ValueError(f"iqa metrics: sigma_n_sq must be positive, got {sigma_n_sq!r}")
     import ctypes
-    srcs = [t.contiguous().float() for t in (input, target, pred)]
+    srcs = _fp32_sources(input, target, pred)
     mask = sum(1 << IQA_METRICS.index(n) for n in which)
     L = _lib.lib()
     dev = srcs[1].device
@@ -228,31 +275,34 @@ def iqa_metrics_per_slice(input, target, pred, which=IQA_METRICS, sigma_n_sq=2.0
     return _iqa_triples(which, iqa_metrics_each(input, target, pred, which, sigma_n_sq).tolist())
 
 
-def _iqa_mean(name, input, target, pred, data_range, **kw):
-    if data_range != 1.0:
-        raise NotImplementedError(f"{name}: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
-    return tuple(iqa_metrics_each(input, target, pred, (name,), **kw)[0].mean(dim=1).tolist())
-
-
 def compute_MS_SSIM(input, target, pred, data_range=1.0):
     """piq's multi_scale_ssim(a, target) with its defaults for a = input, target, pred: (input, gt, pred) floats, each the mean
     over the batch of the per-image scores (reduction='mean').  Sides of at least 161."""
-    return _iqa_mean("ms_ssim", input, target, pred, data_range)
+    return tuple(_batch_means("ms_ssim", data_range, iqa_metrics_each, input, target, pred, ("ms_ssim",)).tolist())
 
 
 def compute_VIF(input, target, pred, data_range=1.0, sigma_n_sq=2.0):
     """piq's vif_p(a, target) likewise.  The vendored vif_p does not rescale to [0, 255]: sigma_n_sq = 2.0 applies to the [0, 1]
     images as they are (iqa_metrics_each).  Sides of at least 41."""
-    return _iqa_mean("vif", input, target, pred, data_range, sigma_n_sq=sigma_n_sq)
+    return tuple(_batch_means("vif", data_range, iqa_metrics_each, input, target, pred, ("vif",), sigma_n_sq=sigma_n_sq).tolist())
 
 
 def compute_GMSD(input, target, pred, data_range=1.0):
     """piq's gmsd(a, target) likewise.  Sides of at least 2."""
-    return _iqa_mean("gmsd", input, target, pred, data_range)
+    return tuple(_batch_means("gmsd", data_range, iqa_metrics_each, input, target, pred, ("gmsd",)).tolist())
 
 
 # ================================================================================================ HaarPSI
 HAARPSI_MIN_SIDE = 16                                           # piq's own limit: 2 ** (scales + 1), checked before the subsampling
+HAARPSI_OPTIONS = ("c", "alpha", "subsample")
+
+
+def haarpsi_check_options(c=30.0, alpha=4.2, subsample=True):
+    """ValueError unless c and alpha are positive finite numbers and subsample a bool."""
+    if not all(_number(v) and v > 0 for v in (c, alpha)):
+        raise ValueError(f"haarpsi: c and alpha must be positive, got {c!r}, {alpha!r}")
+    if not isinstance(subsample, bool):
+        raise ValueError(f"haarpsi: subsample must be a bool, got {subsample!r}")
 
 
 def haarpsi_each(input, target, pred, c=30.0, alpha=4.2, subsample=True, parts=False):
@@ -262,18 +312,13 @@ def haarpsi_each(input, target, pred, c=30.0, alpha=4.2, subsample=True, parts=F
     values depend neither on the batch it is in nor on the other two image sets (mtd_haarpsi_each: fp32 filters; similarity,
     sigmoid and per-image sums in double in a fixed order; two launches for the three pairs of the batch).  Two all-zero images
     give +inf, as piq does.  Sides of at least 16, with subsample or without (ValueError, as piq raises)."""
-    for t in (input, target, pred):
-        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
-            raise AssertionError("haarpsi expects (B,1,H,W) tensors of the same shape")
-        if not t.is_cuda:
-            raise RuntimeError("haarpsi: HIP path needs CUDA tensors (no CPU fallback)")
-    B, _, H, W = target.shape
+    B, H, W = _image_shape("haarpsi expects", input, target, pred)
+    _need_cuda("haarpsi", input, target, pred)
     if H < HAARPSI_MIN_SIDE or W < HAARPSI_MIN_SIDE:
         raise ValueError(f"haarpsi needs images of at least {HAARPSI_MIN_SIDE}x{HAARPSI_MIN_SIDE}, got {H}x{W}")
-    if not c > 0 or not alpha > 0:
-        raise ValueError(f"haarpsi: c and alpha must be positive, got {c!r}, {alpha!r}")
+    haarpsi_check_options(c, alpha, subsample)
     import ctypes
-    srcs = [t.contiguous().float() for t in (input, target, pred)]
+    srcs = _fp32_sources(input, target, pred)
     sub = 1 if subsample else 0
     L = _lib.lib()
     dev = srcs[1].device
@@ -289,16 +334,13 @@ def haarpsi_each(input, target, pred, c=30.0, alpha=4.2, subsample=True, parts=F
 def haarpsi_per_slice(input, target, pred, c=30.0, alpha=4.2, subsample=True):
     """haarpsi_each as host numbers: a list of B (input, gt, pred) triples (the kernels' float64 scores).  One device -> host
     copy for the batch."""
-    vals = haarpsi_each(input, target, pred, c, alpha, subsample).tolist()
-    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+    return _who_triples(haarpsi_each(input, target, pred, c, alpha, subsample).tolist())
 
 
 def compute_HaarPSI(input, target, pred, data_range=1.0, **kw):
     """piq's haarpsi(a, target) with its defaults (or c, alpha, subsample) for a = input, target, pred: (input, gt, pred) floats,
     each the mean over the batch of the per-image scores (reduction='mean').  Sides of at least 16."""
-    if data_range != 1.0:
-        raise NotImplementedError("haarpsi: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
-    return tuple(haarpsi_each(input, target, pred, **kw).mean(dim=1).tolist())
+    return tuple(_batch_means("haarpsi", data_range, haarpsi_each, input, target, pred, **kw).tolist())
 
 
 # ================================================================================================ FSIM
@@ -373,15 +415,10 @@ _fsim_device_tables = {}
 
 
 def _fsim_tables(h, w, scales, orientations, min_length, mult, sigma_f, delta_theta, device):
-    key = (h, w, scales, orientations, min_length, mult, sigma_f, delta_theta, device.index if device.index is not None else torch.cuda.current_device())
-    got = _fsim_device_tables.get(key)
-    if got is None:
+    def build():
         table = fsim_filter_table(h, w, scales, orientations, min_length, mult, sigma_f, delta_theta)
-        got = (table.to(device), fsim_constants(table, scales, orientations).to(device))
-        if len(_fsim_device_tables) >= 16:
-            _fsim_device_tables.clear()
-        _fsim_device_tables[key] = got
-    return got
+        return table.to(device), fsim_constants(table, scales, orientations).to(device)
+    return _device_cached(_fsim_device_tables, (h, w, scales, orientations, min_length, mult, sigma_f, delta_theta), device, build)
 
 
 def fsim_each(input, target, pred, scales=4, orientations=4, min_length=6, mult=2, sigma_f=0.55, delta_theta=1.2, k=2.0, parts=False):
@@ -393,24 +430,15 @@ def fsim_each(input, target, pred, scales=4, orientations=4, min_length=6, mult=
     transformed once.  Two all-zero images give exactly 1, as piq does.  The pooled map (fsim_pooled_size) must have sides that
     are powers of two in 16..512: 64 x 64 patches, 256 x 256, 512 x 512 and 1024 x 1024 slices, 512 x 256 ...; anything else is a
     ValueError that names the pooled size."""
-    for t in (input, target, pred):
-        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
-            raise AssertionError("fsim expects (B,1,H,W) tensors of the same shape")
+    B, H, W = _image_shape("fsim expects", input, target, pred)
     fsim_check_options(scales, orientations, min_length, mult, sigma_f, delta_theta, k)
-    B, _, H, W = target.shape
     ks, h, w = fsim_pooled_size(H, W)
     if not all(FSIM_MIN_SIDE <= n <= FSIM_MAX_SIDE and n & (n - 1) == 0 for n in (h, w)):
         raise ValueError(f"fsim: {H}x{W} images pool (kernel {ks}) to {h}x{w}; the kernels take pooled sides that are powers of two in "
                          f"{FSIM_MIN_SIDE}..{FSIM_MAX_SIDE}")
-    for t in (input, target, pred):
-        if not t.is_cuda:
-            raise RuntimeError("fsim: HIP path needs CUDA tensors (no CPU fallback)")
+    _need_cuda("fsim", input, target, pred)
     import ctypes
-    srcs, kept = [], {}
-    for t in (input, target, pred):                              # (the same tensor twice stays the same pointer: transformed once)
-        if id(t) not in kept:
-            kept[id(t)] = t.contiguous().float()
-        srcs.append(kept[id(t)])
+    srcs = _fp32_sources(input, target, pred)                    # (the same tensor twice stays the same pointer: transformed once)
     L = _lib.lib()
     dev = srcs[1].device
     table, consts = _fsim_tables(h, w, scales, orientations, min_length, mult, sigma_f, delta_theta, dev)
@@ -426,16 +454,13 @@ def fsim_each(input, target, pred, scales=4, orientations=4, min_length=6, mult=
 def fsim_per_slice(input, target, pred, **kw):
     """fsim_each as host numbers: a list of B (input, gt, pred) triples (the kernels' float64 scores).  One device -> host copy
     for the batch."""
-    vals = fsim_each(input, target, pred, **kw).tolist()
-    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+    return _who_triples(fsim_each(input, target, pred, **kw).tolist())
 
 
 def compute_FSIM(input, target, pred, data_range=1.0, **kw):
     """piq's fsim(a, target, chromatic=False) with its defaults (or the seven options) for a = input, target, pred: (input, gt,
     pred) floats, each the mean over the batch of the per-image scores (reduction='mean')."""
-    if data_range != 1.0:
-        raise NotImplementedError("fsim: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
-    return tuple(fsim_each(input, target, pred, **kw).mean(dim=1).tolist())
+    return tuple(_batch_means("fsim", data_range, fsim_each, input, target, pred, **kw).tolist())
 
 
 # ================================================================================================ VSI and MDSI
@@ -453,10 +478,6 @@ def vsi_kernel_size(H, W):
     641 -> 3.  The pooled map has ceil(H / k) x ceil(W / k) pixels: both metrics pad k - 1 pixels per axis before the floor pooling
     (VSI [k // 2, (k - 1) // 2] in replicate mode, MDSI [(k - 1) // 2, k // 2] with zeros)."""
     return max(1, round(min(H, W) / 256))
-
-
-def _number(v):
-    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
 
 
 def vsi_check_options(c1=1.27, c2=386., c3=130., alpha=0.4, beta=0.02, omega_0=0.021, sigma_f=1.34, sigma_d=145., sigma_c=0.001):
@@ -496,34 +517,16 @@ _vsi_device_tables = {}
 
 
 def _vsi_table(omega_0, sigma_f, device):
-    key = (omega_0, sigma_f, device.index if device.index is not None else torch.cuda.current_device())
-    got = _vsi_device_tables.get(key)
-    if got is None:
-        got = vsi_log_gabor_table(omega_0, sigma_f).to(device)
-        if len(_vsi_device_tables) >= 16:
-            _vsi_device_tables.clear()
-        _vsi_device_tables[key] = got
-    return got
+    return _device_cached(_vsi_device_tables, (omega_0, sigma_f), device, lambda: vsi_log_gabor_table(omega_0, sigma_f).to(device))
 
 
 def _each_sources(name, input, target, pred, lo, hi):
-    """The shared argument checks of vsi_each / mdsi_each -> (contiguous fp32 sources, B, H, W); the same tensor twice stays the
-    same pointer."""
-    for t in (input, target, pred):
-        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
-            raise AssertionError(f"{name} expects (B,1,H,W) tensors of the same shape")
-    B, _, H, W = target.shape
+    """The shared argument checks of vsi_each / mdsi_each -> (contiguous fp32 sources, B, H, W)."""
+    B, H, W = _image_shape(f"{name} expects", input, target, pred)
     if not (lo <= H <= hi and lo <= W <= hi):
         raise ValueError(f"{name}: the kernels take images with sides in {lo}..{hi}, got {H}x{W}")
-    for t in (input, target, pred):
-        if not t.is_cuda:
-            raise RuntimeError(f"{name}: HIP path needs CUDA tensors (no CPU fallback)")
-    srcs, kept = [], {}
-    for t in (input, target, pred):
-        if id(t) not in kept:
-            kept[id(t)] = t.contiguous().float()
-        srcs.append(kept[id(t)])
-    return srcs, B, H, W
+    _need_cuda(name, input, target, pred)
+    return _fp32_sources(input, target, pred), B, H, W
 
 
 def vsi_each(input, target, pred, c1=1.27, c2=386., c3=130., alpha=0.4, beta=0.02, omega_0=0.021, sigma_f=1.34, sigma_d=145., sigma_c=0.001,
@@ -578,30 +581,24 @@ def mdsi_each(input, target, pred, c1=140., c2=55., c3=550., combination="sum", 
 def vsi_per_slice(input, target, pred, **kw):
     """vsi_each as host numbers: a list of B (input, gt, pred) triples (the kernels' float64 scores).  One device -> host copy
     for the batch."""
-    vals = vsi_each(input, target, pred, **kw).tolist()
-    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+    return _who_triples(vsi_each(input, target, pred, **kw).tolist())
 
 
 def mdsi_per_slice(input, target, pred, **kw):
     """mdsi_each as host numbers: a list of B (input, gt, pred) triples.  One device -> host copy for the batch."""
-    vals = mdsi_each(input, target, pred, **kw).tolist()
-    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
+    return _who_triples(mdsi_each(input, target, pred, **kw).tolist())
 
 
 def compute_VSI(input, target, pred, data_range=1.0, **kw):
     """piq's vsi(a, target) with its defaults (or the nine options) for a = input, target, pred: (input, gt, pred) floats, each the
     mean over the batch of the per-image scores (reduction='mean')."""
-    if data_range != 1.0:
-        raise NotImplementedError("vsi: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
-    return tuple(vsi_each(input, target, pred, **kw).mean(dim=1).tolist())
+    return tuple(_batch_means("vsi", data_range, vsi_each, input, target, pred, **kw).tolist())
 
 
 def compute_MDSI(input, target, pred, data_range=1.0, **kw):
     """piq's mdsi(a, target) with its defaults (or the ten options) for a = input, target, pred: (input, gt, pred) floats, each
     the mean over the batch of the per-image scores (reduction='mean')."""
-    if data_range != 1.0:
-        raise NotImplementedError("mdsi: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
-    return tuple(mdsi_each(input, target, pred, **kw).mean(dim=1).tolist())
+    return tuple(_batch_means("mdsi", data_range, mdsi_each, input, target, pred, **kw).tolist())
 
 
 # ================================================================================================ perceptual metrics
@@ -1098,12 +1095,8 @@ def dists_finish(tables, pixels, weights, self_row=-1, parts=False):
 def _vgg16_inputs(name, input, target, pred, vgg):
     if not isinstance(vgg, VGG16Features):
         raise TypeError(f"{name}: pass the feature network as vgg=VGG16Features(state_dict) (no pretrained weights ship with this package)")
-    for t in (input, target, pred):
-        if t.dim() != 4 or t.shape != target.shape or t.shape[1] != 1:
-            raise AssertionError(f"{name} expects three (B,1,H,W) tensors of the same shape")
-        if not t.is_cuda:
-            raise RuntimeError(f"{name}: HIP path needs CUDA tensors (no CPU fallback)")
-    H, W = target.shape[2:]
+    _, H, W = _image_shape(f"{name} expects three", input, target, pred)
+    _need_cuda(name, input, target, pred)
     if H < 16 or W < 16:
         raise ValueError(f"{name}: images of at least 16 x 16 expected, got {H} x {W}")
 
@@ -1157,10 +1150,6 @@ def dists_each(input, target, pred, *, vgg, weights, parts=False):
     return dists_finish(tables, [m.shape[1] * m.shape[2] for m in maps], table, self_row=1, parts=parts)
 
 
-def _who_triples(vals):
-    return [tuple(vals[k][i] for k in range(3)) for i in range(len(vals[0]))]
-
-
 def lpips_per_slice(input, target, pred, **kw):
     """lpips_each as host numbers: a list of B (input, gt, pred) triples.  One device -> host copy for the batch."""
     return _who_triples(lpips_each(input, target, pred, **kw).tolist())
@@ -1174,16 +1163,12 @@ def dists_per_slice(input, target, pred, **kw):
 def compute_LPIPS(input, target, pred, data_range=1.0, **kw):
     """piq's LPIPS(reduction='mean')(a, target) for a = input, target, pred: a triple of 0-dim float64 device tensors, each the mean
     over the batch of the per-image scores.  Keywords as lpips_each (vgg, weights, distance)."""
-    if data_range != 1.0:
-        raise NotImplementedError("lpips: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
-    return tuple(lpips_each(input, target, pred, **kw).mean(dim=1).unbind())
+    return tuple(_batch_means("lpips", data_range, lpips_each, input, target, pred, **kw).unbind())
 
 
 def compute_DISTS(input, target, pred, data_range=1.0, **kw):
     """piq's DISTS(reduction='mean')(a, target) likewise.  Keywords as dists_each (vgg, weights)."""
-    if data_range != 1.0:
-        raise NotImplementedError("dists: the kernels are built for data_range 1.0, as the test loop calls the pixel metrics")
-    return tuple(dists_each(input, target, pred, **kw).mean(dim=1).unbind())
+    return tuple(_batch_means("dists", data_range, dists_each, input, target, pred, **kw).unbind())
 
 
 # ================================================================================================ FID

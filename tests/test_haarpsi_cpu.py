@@ -112,6 +112,23 @@ def test_engine_option_values():
     assert engine._iqa_option(types.SimpleNamespace(test_haarpsi=True)) is None          # the two options do not see each other
 
 
+def test_check_options_is_the_one_rule():
+    """metrics.haarpsi_check_options: what the loop's option and haarpsi_each both go by (the latter before it touches a device:
+    the shape and CUDA checks come first, so it is called directly here)."""
+    import numpy as np
+    from mtd_gan_amd import metrics as M
+    assert M.HAARPSI_OPTIONS == ("c", "alpha", "subsample")
+    for ok in (dict(), dict(c=10, alpha=2.0), dict(subsample=False), dict(c=30.0, alpha=4.2, subsample=True), dict(c=np.float64(3.0))):
+        M.haarpsi_check_options(**ok)
+    for bad in (dict(c=0.0), dict(alpha=-4.2), dict(c="30"), dict(alpha=True), dict(c=float("inf")), dict(alpha=float("nan")),
+                dict(c=np.float32(30.0)), dict(alpha=torch.tensor(4.2))):
+        with pytest.raises(ValueError, match="c and alpha must be positive"):
+            M.haarpsi_check_options(**bad)
+    for bad in (1, 0, None, "yes", np.bool_(True)):
+        with pytest.raises(ValueError, match="subsample must be a bool"):
+            M.haarpsi_check_options(subsample=bad)
+
+
 def test_header_declares_and_lib_binds_the_entry_points(built_lib):
     from mtd_gan_amd import _lib
     header = open(os.path.join(ROOT, "include", "mtdgan_hip.h")).read()

@@ -370,3 +370,73 @@ def test_engine_per_slice_with_fid_features(hip_lib, tmp_path):
     for who, v in zip(("input", "gt", "pred"), triple):
         assert v == v and abs(v) != float("inf")
         assert full[f"{who}_fid"] == round(v, 7)
+
+
+# ------------------------------------------------------------------------------ every opt-in per-slice metric at once
+class _Pointwise(torch.nn.Module):
+    """A stand-in generator whose output for a slice has the same bits in any batch (tests/test_iqa_gpu.py's)."""
+
+    def forward(self, x):
+        return 1.05 * x - 0.02
+
+
+def _keys(*names):
+    return [f"{who}_{name}" for name in names for who in ("input", "gt", "pred")]
+
+
+def test_engine_with_every_per_slice_option(hip_lib, tmp_path, monkeypatch):
+    """All seven opt-in metrics of the test loop together, under test_per_slice (batches of 2) and on the default path (batches
+    of 1): the keys and the columns are the per-metric tests' in the loop's order, and every option's meters and CSV column are
+    EQUAL to those of a run with that option alone -- the same code on the same maps, whatever stands beside it in the batch's
+    one host read.  64 x 64 slices, so test_iqa holds VIFp and GMSD (MS-SSIM needs sides of 161)."""
+    import types
+    import _lpips_ref as RL
+    from mtd_gan_amd import engine, metrics as M
+    x, y = orc.synthetic_ldct(4, seed=9, size=64)
+    net = M.VGG16Features(RL.seeded_state_dict())
+    gen = _Pointwise().cuda()
+    options = dict(test_iqa=("gmsd", "vif"), test_haarpsi=True, test_fsim=True, test_lpips=RL.seeded_lpips_weights(),
+                   test_dists=RL.seeded_dists_weights(), test_vsi=True, test_mdsi=True)
+    keys = dict(test_iqa=_keys("vif", "gmsd"), test_haarpsi=_keys("haarpsi"), test_fsim=_keys("fsim"), test_lpips=_keys("lpips"),
+                test_dists=_keys("dists"), test_vsi=_keys("vsi"), test_mdsi=_keys("mdsi"))
+    columns = dict(test_iqa=["VIF", "GMSD"], test_haarpsi=["HaarPSI"], test_fsim=["FSIM"], test_lpips=["LPIPS"], test_dists=["DISTS"],
+                   test_vsi=["VSI"], test_mdsi=["MDSI"])
+
+    def run(tag, per_slice, opts, save=True):
+        m = types.SimpleNamespace(Generator=gen, perceptual_vgg16=net, test_per_slice=per_slice, **opts)
+        d = tmp_path / tag
+        res = engine.test_MTD_GAN_Ours(m, torch.nn.L1Loss(), _loader(x, y, 2 if per_slice else 1)[0], torch.device("cuda"), str(d) if save else None)
+        return res, [ln.split(",") for ln in open(d / "pred_results.csv").read().splitlines()] if save else None
+
+    for per_slice in (True, False):
+        res, rows = run(f"all_{per_slice}", per_slice, options)
+        assert list(res.keys()) == PIXEL_KEYS + sum(keys.values(), [])
+        assert ",".join(rows[0]) == ",PATH,RMSE,PSNR,SSIM,VIF,GMSD,HaarPSI,FSIM,LPIPS,DISTS,VSI,MDSI" and len(rows) == 5
+        at = 5
+        for attr, value in options.items():
+            one, one_rows = run(f"{attr}_{per_slice}", per_slice, {attr: value})
+            n = len(columns[attr])
+            assert list(one.keys()) == PIXEL_KEYS + keys[attr] and one_rows[0] == ["", "PATH", "RMSE", "PSNR", "SSIM"] + columns[attr]
+            assert {k: res[k] for k in PIXEL_KEYS + keys[attr]} == one, attr
+            assert [r[:5] + r[at:at + n] for r in rows] == one_rows, attr
+            at += n
+        assert at == len(rows[0])
+        if per_slice:
+            each = res
+
+    # the batch's one host read under test_per_slice: 7 pixel values and 3 x 8 of the options per slice
+    reads = []
+
+    def counted(name):
+        real = getattr(torch.Tensor, name)
+
+        def wrapper(self, *a, **kw):
+            if self.is_cuda:
+                reads.append((name, tuple(self.shape)))
+            return real(self, *a, **kw)
+        monkeypatch.setattr(torch.Tensor, name, wrapper)
+    for name in ("tolist", "item", "cpu", "numpy", "__float__"):
+        counted(name)
+    again, _ = run("counted", True, options, save=False)
+    assert reads == [("tolist", ((7 + 3 * 8) * 2,))] * 2, reads
+    assert again == each
