@@ -646,6 +646,39 @@ size_t mtd_mdsi_ws_bytes(int na, int B, int H, int W, int k);
 int mtd_mdsi_each(const void* const* srcs, int na, const void* target, int B, int H, int W, int k, const double* options, int mult,
                   double* out, double* parts, void* ws, void* stream);
 
+/* ---- the no-reference statistics of the test loop (module/piq: brisque.py brisque, tv.py total_variation) -- DESIGN 3.21.
+ * Single-channel fp32 images (B, H, W) in [0, 1] (data_range 1), na in 1..3 sources srcs[k], each on its own (there is no target),
+ * image by image.  srcs is read on the host during the call (its first na entries); a pointer that occurs twice is computed once
+ * and written to both slots.  Everything is double, every per-image sum in a fixed order: an image's numbers depend neither on the
+ * batch nor on its source slot.
+ * mtd_brisque_each: ks: the odd side 3..MTD_BRISQUE_MAX_KERNEL of the Gaussian filter, taps: device, its ks * ks fp32 taps (piq's
+ *   gaussian_filter, normalised); tables: device, 3 * nt doubles: piq's gamma grid, the GGD r_table, the AGGD r_table; weights:
+ *   device, (n_sv, 37) doubles: the SVR coefficient, then the support vector.  Two scales: 255 * image, and its `nearest` resample
+ *   to (H / 2, W / 2) (source index min(floor(dst * scale), size - 1), scale = size / (size / 2) in fp32).  out: (na, B) doubles.
+ *   parts (optional, may be null): (na, B, MTD_BRISQUE_PARTS) doubles: the 36 features before the range scaling (per scale alpha,
+ *   sigma^2, then per shift alpha, eta, sigma_l^2, sigma_r^2), then the score.  Where piq asserts (an MSCN map whose sigma is within
+ *   1e-8 of zero, a product map without a negative or without a positive value, a zero left or right sigma) the image's score
+ *   and parts are NaN; the other images are untouched.  The batch is walked in chunks sized so that the workspace (the _ws_bytes
+ *   query) stays within 64 MiB.
+ * mtd_tv_each: norm: MTD_TV_L1 (sum |dy| + sum |dx|), MTD_TV_L2 (the square root of sum dy^2 + sum dx^2), MTD_TV_L2_SQUARED, of
+ *   the differences of neighbouring pixels of the image itself (not scaled).  out: (na, B) doubles.
+ * Null pointers, na outside 1..3, B < 1, a side outside MTD_*_MIN_SIDE .. MTD_*_MAX_SIDE, an even ks or one outside its range,
+ * nt < 1, n_sv < 1, another norm: MTD_EINVAL before any launch (the _ws_bytes query then returns 0). */
+#define MTD_BRISQUE_MIN_SIDE 16
+#define MTD_BRISQUE_MAX_SIDE 1024
+#define MTD_BRISQUE_MAX_KERNEL 15
+#define MTD_BRISQUE_PARTS 37
+#define MTD_TV_MIN_SIDE 16
+#define MTD_TV_MAX_SIDE 1024
+#define MTD_TV_L1 0
+#define MTD_TV_L2 1
+#define MTD_TV_L2_SQUARED 2
+size_t mtd_brisque_ws_bytes(int na, int B, int H, int W);
+int mtd_brisque_each(const void* const* srcs, int na, int B, int H, int W, int ks, const float* taps, const double* tables, int nt,
+                     const double* weights, int n_sv, double* out, double* parts, void* ws, void* stream);
+size_t mtd_tv_ws_bytes(int na, int B, int H, int W);
+int mtd_tv_each(const void* const* srcs, int na, int B, int H, int W, int norm, double* out, void* ws, void* stream);
+
 /* ---- perceptual metrics of the test loop (metrics.py:43-168: PL and TML on VGG-19 features; engine.py:139-140) ------
  * The convolutions of the feature stack are mtd_conv_* launches; these are the other pieces.  Maps are contiguous NHWC fp32,
  * 16-byte aligned (MTD_EALIGN).

@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 LAB_BUILD = os.environ.get("MTD_LAB_BUILD", "0") == "1"
 LIB = os.path.join(HERE, "libmtdgan_hip_lab.so" if LAB_BUILD else "libmtdgan_hip.so")
 SOURCES = ["conv_igemm.hip", "conv_wgrad.hip", "conv_c32_bwd.hip", "conv_winograd.hip", "conv_direct.hip", "resfft.hip", "resfft4.hip", "resfft_any.hip", "resfft_gen.hip", "elementwise.hip",
-           "specnorm.hip", "losses.hip", "metrics.hip", "iqa.hip", "haarpsi.hip", "fsim.hip", "vsi.hip", "mdsi.hip", "perceptual.hip", "lpips.hip", "fid.hip", "kid.hip", "msid.hip", "inception.hip", "sampler.hip", "png_gray.hip", "dicom_domain.hip", "sliding_window.hip", "pcgrad.hip", "weighting.hip", "adamw.hip", "api.hip"]
+           "specnorm.hip", "losses.hip", "metrics.hip", "iqa.hip", "haarpsi.hip", "fsim.hip", "vsi.hip", "mdsi.hip", "brisque.hip", "perceptual.hip", "lpips.hip", "fid.hip", "kid.hip", "msid.hip", "inception.hip", "sampler.hip", "png_gray.hip", "dicom_domain.hip", "sliding_window.hip", "pcgrad.hip", "weighting.hip", "adamw.hip", "api.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 

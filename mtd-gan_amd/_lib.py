@@ -293,6 +293,10 @@ def lib():
     sig("mtd_vsi_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, vp, C.POINTER(C.c_double), vp, vp, vp, vp)
     sig("mtd_mdsi_ws_bytes", sz, ci, ci, ci, ci, ci)
     sig("mtd_mdsi_each", ci, C.POINTER(vp), ci, vp, ci, ci, ci, ci, C.POINTER(C.c_double), ci, vp, vp, vp, vp)
+    sig("mtd_brisque_ws_bytes", sz, ci, ci, ci, ci)
+    sig("mtd_brisque_each", ci, C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp)
+    sig("mtd_tv_ws_bytes", sz, ci, ci, ci, ci)
+    sig("mtd_tv_each", ci, C.POINTER(vp), ci, ci, ci, ci, ci, vp, vp, vp)
     sig("mtd_maxpool2x2", ci, vp, vp, ci, ci, ci, ci, vp)
     sig("mtd_patch_gram_l1_ws_bytes", sz, ci, ci, ci, ci)
     sig("mtd_patch_gram_l1", ci, vp, vp, ci, ci, ci, ci, vp, vp, vp)
@@ -413,6 +417,7 @@ EXPORTS = [
     "mtd_haarpsi_ws_bytes", "mtd_haarpsi_each",
     "mtd_fsim_ws_bytes", "mtd_fsim_each", "mtd_fsim_median",
     "mtd_vsi_ws_bytes", "mtd_vsi_each", "mtd_mdsi_ws_bytes", "mtd_mdsi_each",
+    "mtd_brisque_ws_bytes", "mtd_brisque_each", "mtd_tv_ws_bytes", "mtd_tv_each",
     "mtd_l2pool3x3s2", "mtd_lpips_level_ws_bytes", "mtd_lpips_level_each", "mtd_scaled_sums_f64_f64",
     "mtd_channel_moments_ws_bytes", "mtd_channel_moments_each", "mtd_dists_finish",
 ]

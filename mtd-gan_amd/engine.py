@@ -355,6 +355,30 @@ def _lpips_form(e, cfg):
     return cfg, dict(distance=distance)
 
 
+def _brisque_parse(model, e):
+    """`model.test_brisque`: absent, None, False or empty -> None; the support vector regression in a form metrics.brisque_weights
+    takes, or `dict(weights=..., kernel_size=..., kernel_sigma=...)` -> the keyword arguments of metrics.brisque_each, the float64
+    table under `weights`.  True: ValueError, no weights ship with this package."""
+    from . import metrics as M
+    cfg = getattr(model, e.attr, None)
+    if cfg is None or cfg is False or (isinstance(cfg, (dict, list, tuple, str)) and not cfg):
+        return None
+    more = {}
+    if isinstance(cfg, dict):
+        if set(cfg) - {"weights", *M.BRISQUE_OPTIONS} or "weights" not in cfg:
+            raise ValueError(f"model.{e.attr}: the weights, or a dict with the keys weights, {', '.join(M.BRISQUE_OPTIONS)}; got the keys {sorted(cfg)}")
+        more = {k: v for k, v in cfg.items() if k != "weights"}
+        cfg = cfg["weights"]
+    if cfg is True:
+        raise ValueError(f"model.{e.attr}: no weights ship with this package; pass {e.text}")
+    try:
+        M.brisque_check_options(**more)
+        table = M.brisque_weights(cfg)
+    except (ValueError, OSError) as err:
+        raise ValueError(f"model.{e.attr}: {err}") from None
+    return dict(weights=table, **more)
+
+
 _PER_SLICE = (
     _PerSlice("test_iqa", _iqa_parse, "iqa_metrics_each", {"ms_ssim": "MS_SSIM", "vif": "VIF", "gmsd": "GMSD"}, "True or a tuple of names from"),
     _PerSlice("test_haarpsi", _checked_parse, "haarpsi_each", {"haarpsi": "HaarPSI"}, "c, alpha (positive numbers), subsample (a bool)"),
@@ -366,6 +390,8 @@ _PER_SLICE = (
               "c1, c2, c3, omega_0, sigma_f, sigma_d, sigma_c (positive numbers), alpha, beta (numbers)"),
     _PerSlice("test_mdsi", _checked_parse, "mdsi_each", {"mdsi": "MDSI"},
               "c1, c2, c3, rho (positive numbers), combination ('sum' or 'mult'), alpha, beta, gamma, q, o (numbers)"),
+    _PerSlice("test_brisque", _brisque_parse, "brisque_each", {"brisque": "BRISQUE"}, "BRISQUE's (sv_coef, sv) pair or a path to it"),
+    _PerSlice("test_tv", _checked_parse, "tv_each", {"tv": "TV"}, "norm_type ('l1', 'l2' or 'l2_squared')"),
 )
 
 
@@ -651,6 +677,14 @@ def test_MTD_GAN_Ours(model, loss, data_loader, device, save_dir):
     per image set (the mean over its slices, one more host read each); under `test_per_slice` the 3 B values of each travel in
     the batch's one device -> host copy, behind the DISTS block.  Slices with sides in 16..1024 (ValueError otherwise).  Any other
     value of either attribute is refused (ValueError) before anything runs; without them (or with falsy values) nothing changes.
+    `model.test_brisque = <weights>` (piq's (sv_coef, sv) pair of the support vector regression or a path to it, or
+    `dict(weights=..., kernel_size=..., kernel_sigma=...)`; none ships with this package) and `model.test_tv = True` (or
+    `dict(norm_type="l1" | "l2" | "l2_squared")`) add the reference's vendored piq no-reference metrics BRISQUE and
+    total variation of input, gt and the clipped prediction, each on its own, on the HIP kernels of csrc/brisque.hip
+    (metrics.brisque_each / tv_each): the result gains {input,gt,pred}_brisque and {input,gt,pred}_tv after the MDSI keys (before
+    the FID / KID keys) and the CSV the columns BRISQUE and TV after MDSI, holding the prediction's values.  A slice on which piq
+    would assert (a constant one) has the BRISQUE value NaN.  Batches as for VSI and MDSI; sides in 16..1024.  Any other value
+    of either attribute is refused (ValueError) before anything runs; without them (or with None / False) nothing changes.
     `model.test_kid = True` (or a dict of metrics.kid_distance64's keyword arguments) adds piq's Kernel Inception
     Distance after the loop, from the same feature rows as FID and therefore only with `model.fid_features` (ValueError
     otherwise, before anything runs): the result gains input_kid / gt_kid / pred_kid behind the FID keys (metrics.compute_KID:

@@ -47,6 +47,13 @@ similarity index, image by image on the HIP kernels of csrc/vsi.hip and csrc/mds
 `model.test_vsi` / `model.test_mdsi`).  SDSP's log-Gabor table is built on the host once per (omega_0, sigma_f) and uploaded once
 per device (vsi_log_gabor_table).
 
+BRISQUE (module/piq/brisque.py: brisque) and total variation (module/piq/tv.py: total_variation), the two no-reference metrics,
+image by image and each image set on its own on the HIP kernels of csrc/brisque.hip (`mtd_brisque_each`, `mtd_tv_each`; DESIGN
+3.21): brisque_each / brisque_per_slice / compute_BRISQUE and tv_each / tv_per_slice / compute_TV (engine.test_MTD_GAN_Ours under
+`model.test_brisque` / `model.test_tv`).  BRISQUE's support vector regression is the caller's (brisque_weights); the Gaussian
+filter and the shape look-up tables are built on the host with piq's roundings and uploaded once per device
+(brisque_gaussian_table / brisque_ggd_tables).
+
 LPIPS and DISTS (module/piq/perceptual.py: LPIPS and DISTS on torchvision's VGG-16 with ImageNet normalisation) image by image
 (DESIGN 3.18): the feature stack is `VGG16Features`, built like `VGG19Features` from a state dict the caller hands over, with the
 normalisation folded exactly into its first layer and max or L2 pooling (`mtd_l2pool3x3s2`); the reductions over the maps run on
@@ -521,7 +528,7 @@ def _vsi_table(omega_0, sigma_f, device):
 
 
 def _each_sources(name, input, target, pred, lo, hi):
-    """The shared argument checks of vsi_each / mdsi_each -> (contiguous fp32 sources, B, H, W)."""
+    """The shared argument checks of vsi_each / mdsi_each / brisque_each / tv_each -> (contiguous fp32 sources, B, H, W)."""
     B, H, W = _image_shape(f"{name} expects", input, target, pred)
     if not (lo <= H <= hi and lo <= W <= hi):
         raise ValueError(f"{name}: the kernels take images with sides in {lo}..{hi}, got {H}x{W}")
@@ -599,6 +606,155 @@ def compute_MDSI(input, target, pred, data_range=1.0, **kw):
     """piq's mdsi(a, target) with its defaults (or the ten options) for a = input, target, pred: (input, gt, pred) floats, each
     the mean over the batch of the per-image scores (reduction='mean')."""
     return tuple(_batch_means("mdsi", data_range, mdsi_each, input, target, pred, **kw).tolist())
+
+
+# ================================================================================================ BRISQUE and total variation
+BRISQUE_MIN_SIDE, BRISQUE_MAX_SIDE = 16, 1024
+BRISQUE_PARTS = 37                                              # the 36 features before the range scaling, then the score
+BRISQUE_OPTIONS = ("kernel_size", "kernel_sigma")
+BRISQUE_MAX_KERNEL = 15
+TV_MIN_SIDE, TV_MAX_SIDE = 16, 1024
+TV_NORMS = ("l1", "l2", "l2_squared")                           # the order of MTD_TV_L1, MTD_TV_L2, MTD_TV_L2_SQUARED
+TV_OPTIONS = ("norm_type",)
+
+
+def brisque_check_options(kernel_size=7, kernel_sigma=7 / 6, interpolation="nearest"):
+    """ValueError unless kernel_size is an odd int in 3..15, kernel_sigma a positive finite number and interpolation 'nearest'
+    (the one resampling rule the kernels have)."""
+    if interpolation != "nearest":
+        raise ValueError(f"brisque: the kernels resample with interpolation 'nearest' only, got {interpolation!r}")
+    if not (isinstance(kernel_size, int) and not isinstance(kernel_size, bool) and 3 <= kernel_size <= BRISQUE_MAX_KERNEL and kernel_size % 2 == 1):
+        raise ValueError(f"brisque: kernel_size must be an odd int in 3..{BRISQUE_MAX_KERNEL}, got {kernel_size!r}")
+    if not (_number(kernel_sigma) and kernel_sigma > 0):
+        raise ValueError(f"brisque: kernel_sigma must be a positive number, got {kernel_sigma!r}")
+
+
+def tv_check_options(norm_type="l2"):
+    """ValueError unless norm_type is one of TV_NORMS."""
+    if not (isinstance(norm_type, str) and norm_type in TV_NORMS):
+        raise ValueError(f"tv: norm_type must be one of {TV_NORMS}, got {norm_type!r}")
+
+
+@functools.lru_cache(maxsize=16)
+def brisque_gaussian_table(kernel_size=7, kernel_sigma=7 / 6):
+    """The (kernel_size, kernel_size) float32 host table of the MSCN map's Gaussian filter, normalised to sum 1 in two dimensions:
+    float32 throughout and each element through piq's sequence of roundings (functional/filters.py: gaussian_filter), so the bytes
+    are those of piq's own filter (tests/golden/brisque_tv_piq.npz holds their CRC-32).  Cached; do not modify the result."""
+    brisque_check_options(kernel_size, kernel_sigma)
+    c = torch.arange(kernel_size).to(dtype=torch.float32)
+    c -= (kernel_size - 1) / 2.
+    sq = c ** 2
+    table = (-(sq.unsqueeze(0) + sq.unsqueeze(1)) / (2 * kernel_sigma ** 2)).exp()
+    table /= table.sum()
+    return table.contiguous()
+
+
+@functools.lru_cache(maxsize=1)
+def brisque_ggd_tables():
+    """The (3, 9801) float64 host table of the shape look-ups: piq's grid gamma = arange(0.2, 10.001, 0.001) -- built in float32
+    and widened, as piq's `.to(x)` widens it in a float64 run --, the generalised Gaussian's r(gamma) = G(1/g) G(3/g) / G(2/g)^2
+    and the asymmetric one's G(2/g)^2 / (G(1/g) G(3/g)), both by piq's expressions on lgamma in float64.  Cached; do not modify."""
+    gamma = torch.arange(0.2, 10.001, 0.001).double()
+    one, two, three = torch.lgamma(1. / gamma), torch.lgamma(2. / gamma), torch.lgamma(3. / gamma)
+    return torch.stack([gamma, (one + three - 2 * two).exp(), torch.exp(2 * two - one - three)]).contiguous()
+
+
+def brisque_weights(obj):
+    """The support vector regression of BRISQUE as one (n_sv, 37) float64 table, column 0 the coefficient and columns 1..36 the
+    support vector: `obj` is piq's (sv_coef, sv) pair -- floating-point tensors of shapes (n_sv,) or (n_sv, 1), and (n_sv, 36) --,
+    a path that torch.load reads to such a pair (the format of piq's brisque_svm_weights.pt), or a table this function returned.
+    ValueError otherwise, for a non-finite entry and for n_sv == 0.  No weights ship with this package, and the published file
+    was never seen here: the layout is the one module/piq/brisque.py reads."""
+    obj = _load_weights_file(obj)
+    checked = torch.is_tensor(obj) and obj.dtype == torch.float64 and obj.dim() == 2 and obj.shape[1] == 37
+    if checked:
+        table = obj.detach()
+    else:
+        if not isinstance(obj, (list, tuple)) or len(obj) != 2 or not all(torch.is_tensor(t) and t.is_floating_point() for t in obj):
+            raise ValueError("brisque_weights: a pair (sv_coef, sv) of floating-point tensors expected, got "
+                             f"{[tuple(t.shape) for t in obj] if isinstance(obj, (list, tuple)) and all(torch.is_tensor(t) for t in obj) else type(obj).__name__}")
+        coef, sv = obj
+        if sv.dim() != 2 or sv.shape[1] != 36 or tuple(coef.shape) not in ((sv.shape[0],), (sv.shape[0], 1)):
+            raise ValueError(f"brisque_weights: sv_coef of shape (n_sv,) or (n_sv, 1) and sv of shape (n_sv, 36) expected, got "
+                             f"{tuple(coef.shape)} and {tuple(sv.shape)}")
+        table = torch.cat([coef.detach().double().reshape(-1, 1), sv.detach().double()], dim=1)
+    if table.shape[0] == 0:
+        raise ValueError("brisque_weights: no support vector (n_sv == 0)")
+    if not (checked and table.is_cuda) and not bool(torch.isfinite(table).all()):       # (no host read for a table already on the device)
+        raise ValueError("brisque_weights: a coefficient or support vector entry is not finite")
+    return table.contiguous()
+
+
+_brisque_device_tables = {}
+
+
+def brisque_each(input, target, pred, *, weights, kernel_size=7, kernel_sigma=7 / 6, interpolation="nearest", parts=False):
+    """BRISQUE (piq's brisque, data_range 1, two scales) of every slice of input, target and pred, each image set on its own (the
+    metric has no reference image), without a host read: a (3, B) float64 device tensor.  `weights`: the support vector regression
+    in a form brisque_weights takes (the caller's: none ships with this package).  With parts=True also the (3, B, 37) float64
+    rows: the 36 features before the range scaling (per scale alpha, sigma^2, then for the shifts (0,1), (1,0), (1,1), (-1,1) alpha,
+    eta, sigma_l^2, sigma_r^2), then the score.  All double in a fixed order (mtd_brisque_each): a slice's values depend neither on
+    the batch it is in nor on the other two image sets; an image set passed twice is computed once.
+    One deviation from piq: where piq asserts -- an MSCN map of zero variance (its first assert is `.all()` over the batch, which
+    would make a slice depend on its batch), a product map without a negative or a positive value, a zero left or right sigma --
+    the slice's score and parts are NaN and the other slices are untouched.  Sides in 16..1024, kernel_size odd in 3..15,
+    interpolation 'nearest'; anything else is a ValueError."""
+    import ctypes
+    brisque_check_options(kernel_size, kernel_sigma, interpolation)
+    table = brisque_weights(weights)
+    srcs, B, H, W = _each_sources("brisque", input, target, pred, BRISQUE_MIN_SIDE, BRISQUE_MAX_SIDE)
+    L = _lib.lib()
+    dev = srcs[1].device
+    table = table.to(dev)
+    taps = _device_cached(_brisque_device_tables, ("taps", kernel_size, float(kernel_sigma)), dev,
+                          lambda: brisque_gaussian_table(kernel_size, kernel_sigma).to(dev))
+    ggd = _device_cached(_brisque_device_tables, ("ggd",), dev, lambda: brisque_ggd_tables().to(dev))
+    out = torch.empty((3, B), dtype=torch.float64, device=dev)
+    rows = torch.empty((3, B, BRISQUE_PARTS), dtype=torch.float64, device=dev) if parts else None
+    ws = K.workspace(L.mtd_brisque_ws_bytes(3, B, H, W), dev)
+    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    _lib.check(L.mtd_brisque_each(ptrs, 3, B, H, W, kernel_size, taps.data_ptr(), ggd.data_ptr(), ggd.shape[1], table.data_ptr(), table.shape[0],
+                                  out.data_ptr(), rows.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_brisque_each")
+    return (out, rows) if parts else out
+
+
+def tv_each(input, target, pred, norm_type="l2"):
+    """Total variation (piq's total_variation) of every slice of input, target and pred, each image set on its own, without a host
+    read: a (3, B) float64 device tensor.  norm_type 'l1': the sum of |dy| and |dx| of neighbouring pixels; 'l2': the square root of
+    the sum of their squares; 'l2_squared': that sum.  All double in a fixed order (mtd_tv_each): a slice's value depends neither
+    on the batch it is in nor on the other two image sets; a constant slice gives exactly 0.  Sides in 16..1024 (ValueError)."""
+    import ctypes
+    tv_check_options(norm_type)
+    srcs, B, H, W = _each_sources("tv", input, target, pred, TV_MIN_SIDE, TV_MAX_SIDE)
+    L = _lib.lib()
+    dev = srcs[1].device
+    out = torch.empty((3, B), dtype=torch.float64, device=dev)
+    ws = K.workspace(L.mtd_tv_ws_bytes(3, B, H, W), dev)
+    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    _lib.check(L.mtd_tv_each(ptrs, 3, B, H, W, TV_NORMS.index(norm_type), out.data_ptr(), ws.data_ptr(), K.stream_ptr()), "mtd_tv_each")
+    return out
+
+
+def brisque_per_slice(input, target, pred, **kw):
+    """brisque_each as host numbers: a list of B (input, gt, pred) triples.  One device -> host copy for the batch."""
+    return _who_triples(brisque_each(input, target, pred, **kw).tolist())
+
+
+def tv_per_slice(input, target, pred, **kw):
+    """tv_each as host numbers: a list of B (input, gt, pred) triples.  One device -> host copy for the batch."""
+    return _who_triples(tv_each(input, target, pred, **kw).tolist())
+
+
+def compute_BRISQUE(input, target, pred, data_range=1.0, **kw):
+    """piq's brisque(a) with its defaults (or kernel_size, kernel_sigma) on the caller's `weights` for a = input, target, pred:
+    (input, gt, pred) floats, each the mean over the batch of the per-image scores (reduction='mean')."""
+    return tuple(_batch_means("brisque", data_range, brisque_each, input, target, pred, **kw).tolist())
+
+
+def compute_TV(input, target, pred, data_range=1.0, **kw):
+    """piq's total_variation(a, norm_type=...) for a = input, target, pred: (input, gt, pred) floats, each the mean over the batch
+    of the per-image values (reduction='mean')."""
+    return tuple(_batch_means("tv", data_range, tv_each, input, target, pred, **kw).tolist())
 
 
 # ================================================================================================ perceptual metrics
