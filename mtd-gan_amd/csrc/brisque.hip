@@ -9,7 +9,7 @@
 // and of its nearest-neighbour half-size resample (gathered while loading) into the workspace; the 26 moments of n and of its four
 // circularly shifted products per tile; one workgroup per image for the tile sums, the ten table look-ups (torch.argmin's first
 // minimum), the 36 features, their range scaling and the SVR score.  TV: row-group partial sums, then one small finish.
-#include "common.h"
+#include "each_metric.h"
 #include <math.h>
 
 #pragma clang fp contract(off)      // products and sums rounded one by one, as the float64 tensor operations of piq round them
@@ -25,13 +25,11 @@ constexpr int BQ_MIN_N = MTD_BRISQUE_MIN_SIDE, BQ_MAX_N = MTD_BRISQUE_MAX_SIDE;
 constexpr long long BQ_WS_TARGET = 64LL << 20;
 
 struct BqSrcs {
-    const float* p[3];          // the distinct source pointers
+    EachSets set;               // the distinct source pointers
     int nu;                     // how many
     int count[3];               // output slots of each
     int slot[3][3];
 };
-
-__device__ __forceinline__ const float* pick(const BqSrcs& s, int k) { return k == 0 ? s.p[0] : (k == 1 ? s.p[1] : s.p[2]); }
 
 struct BqGeo { int H, W, h2, w2, tx0, ty0, tx1, ty1, tiles0, tiles1; float sy, sx; };
 
@@ -73,7 +71,7 @@ __global__ __launch_bounds__(256) void brisque_mscn_kernel(BqSrcs srcs, int Bc, 
     __shared__ double X[BQ_HL * BQ_HL];
     __shared__ double T[BQ_MAXK * BQ_MAXK];
     const int s = blockIdx.y / Bc, i = blockIdx.y - s * Bc;
-    const float* __restrict__ img = pick(srcs, s) + (long long)(i0 + i) * g.H * g.W;
+    const float* __restrict__ img = each_pick(srcs.set, s) + (long long)(i0 + i) * g.H * g.W;
     const int sc = (int)blockIdx.x >= g.tiles0;
     const int tile = sc ? blockIdx.x - g.tiles0 : blockIdx.x;
     const int h = sc ? g.h2 : g.H, w = sc ? g.w2 : g.W, tx = sc ? g.tx1 : g.tx0;
@@ -289,7 +287,7 @@ struct BqPlan {
 };
 
 // The workspace holds, per source and image of a chunk, the two MSCN maps and BQ_M doubles per tile.  Bc is the largest count for
-// which that stays within 64 MiB, at least 1, at most B and 8192 (na * Bc indexes a grid dimension).
+// which that stays within 64 MiB (each_chunk).
 BqPlan brisque_plan(int na, int B, int H, int W) {
     BqPlan p = {};
     if (na < 1 || na > 3 || B < 1 || B > (1 << 24)) return p;
@@ -309,10 +307,7 @@ BqPlan brisque_plan(int na, int B, int H, int W) {
     g.tiles1 = g.tx1 * g.ty1;
     p.per_image = (long long)H * W + (long long)g.h2 * g.w2;
     const long long bytes_per = (long long)na * 8 * (p.per_image + (long long)(g.tiles0 + g.tiles1) * BQ_M);
-    long long Bc = BQ_WS_TARGET / bytes_per;
-    Bc = Bc < 1 ? 1 : (Bc > B ? B : Bc);
-    if (Bc > 8192) Bc = 8192;
-    p.Bc = (int)Bc;
+    const long long Bc = p.Bc = each_chunk(BQ_WS_TARGET, bytes_per, B);
     p.partial = (long long)na * Bc * p.per_image * 8;
     p.bytes = p.partial + (long long)na * Bc * (g.tiles0 + g.tiles1) * BQ_M * 8;
     p.ok = true;
@@ -325,8 +320,8 @@ bool distinct_sources(const void* const* srcs, int na, BqSrcs& u) {
     for (int a = 0; a < na; ++a) {
         if (!srcs[a]) return false;
         int k = 0;
-        while (k < u.nu && u.p[k] != (const float*)srcs[a]) ++k;
-        if (k == u.nu) u.p[u.nu++] = (const float*)srcs[a];
+        while (k < u.nu && u.set.p[k] != (const float*)srcs[a]) ++k;
+        if (k == u.nu) u.set.p[u.nu++] = (const float*)srcs[a];
         u.slot[k][u.count[k]++] = a;
     }
     return true;
@@ -340,7 +335,7 @@ constexpr int TV_ROWS = 8;                                     // rows of an ima
 __global__ __launch_bounds__(256) void tv_rows_kernel(BqSrcs srcs, int B, int H, int W, double* __restrict__ partial) {
     __shared__ double red[4 * 4], tot[4];
     const int s = blockIdx.x / B, i = blockIdx.x - s * B;
-    const float* __restrict__ img = pick(srcs, s) + (long long)i * H * W;
+    const float* __restrict__ img = each_pick(srcs.set, s) + (long long)i * H * W;
     const int y0 = blockIdx.y * TV_ROWS;
     const int rows = H - y0 < TV_ROWS ? H - y0 : TV_ROWS;
     double v[4] = {0.0, 0.0, 0.0, 0.0};

@@ -24,11 +24,9 @@
 //                          launch (one workgroup) finishes the residual, forms err, the trace of the square root and the round
 //                          count, and sets "done" when err <= 1e-5.  The host enqueues max_iters rounds and never reads back in
 //                          between.
-#include "common.h"
+#include "gram64.h"          // f64x4
 
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int FT = 64;                  // tile side
 constexpr int FK = 16;                  // k per stage

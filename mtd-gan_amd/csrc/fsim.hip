@@ -15,7 +15,7 @@
 //     torch.median takes it.
 // Launches per chunk of the batch: rows forward (pooling on load), columns forward, filter + columns inverse, rows inverse +
 // energy (one workgroup per orientation and row tile), thresholds, combine, finish.  The responses themselves are never stored; the column-transformed filtered spectra are.
-#include "common.h"
+#include "each_metric.h"
 #include "lds_fft.h"          // fs_brev, fs_twiddles, fs_lds_fft
 #include <float.h>
 #include <math.h>
@@ -32,12 +32,6 @@ constexpr int FS_CT = 16;                     // the combine tile: 16 x 16 pixel
 constexpr int FS_SUMS = 4;                    // num, den, sum pc_a, sum gm_a
 constexpr long long FS_WS_TARGET = 64LL << 20;
 
-struct FsImgs { const float* p[4]; };         // the distinct image sets, B images each
-struct FsMap { int src[3]; int tgt; };        // set of source k, set of the target
-
-__device__ __forceinline__ const float* pick(const FsImgs& s, int k) { return k == 0 ? s.p[0] : (k == 1 ? s.p[1] : (k == 2 ? s.p[2] : s.p[3])); }
-__device__ __forceinline__ int pick(const FsMap& m, int k) { return k == 0 ? m.src[0] : (k == 1 ? m.src[1] : m.src[2]); }
-
 // Pixel (y, x) of the pooled map: the ks x ks block of 255 * image summed row by row and divided by ks^2 (avg_pool2d with
 // stride ks, floor: 0 <= y < H / ks, 0 <= x < W / ks, so the block is inside the image).  The products are rounded on their own.
 __device__ __forceinline__ float fs_pixel(const float* __restrict__ img, int W, int ks, int y, int x) {
@@ -50,13 +44,13 @@ __device__ __forceinline__ float fs_pixel(const float* __restrict__ img, int W, 
 }
 
 // ---- 1. pool on load + forward rows.  grid (h / L, sets * Bc); slot = set * Bc + image of the chunk.
-__global__ __launch_bounds__(256) void fsim_rows_fwd_kernel(FsImgs imgs, int Bc, int i0, int H, int W, int ks, int h, int lw, int L,
+__global__ __launch_bounds__(256) void fsim_rows_fwd_kernel(EachSets imgs, int Bc, int i0, int H, int W, int ks, int h, int lw, int L,
                                                             float2* __restrict__ spec) {
     __shared__ float2 buf[FS_TILE_PTS + 256];
     __shared__ float2 tw[256];
     const int w = 1 << lw, ld = w + 1;
     const int slot = blockIdx.y, set = slot / Bc, i = slot - set * Bc;
-    const float* __restrict__ img = pick(imgs, set) + (long long)(i0 + i) * H * W;
+    const float* __restrict__ img = each_pick(imgs, set) + (long long)(i0 + i) * H * W;
     const int y0 = blockIdx.x * L;
     fs_twiddles(tw, w);
     for (int e = threadIdx.x; e < (L << lw); e += 256) {
@@ -248,12 +242,6 @@ __device__ __forceinline__ double fs_pc(const float* __restrict__ en, const floa
     return (e + eps) / (a + eps);
 }
 
-// piq's similarity_map.  Without contraction into fused multiply-adds, so that equal maps give a ratio of exactly 1.
-__device__ __forceinline__ double fs_similarity(double a, double b, double c) {
-#pragma clang fp contract(off)
-    return (2.0 * a * b + c) / (a * a + b * b + c);
-}
-
 __device__ __forceinline__ double fs_scharr(const float* P) {          // P: the pixel's row in the 18-wide halo tile, at its column
     constexpr int HL = FS_CT + 2;
     const double a = P[-HL - 1], b = P[-HL], c = P[-HL + 1], d = P[-1], f = P[1], g = P[HL - 1], hh = P[HL], i = P[HL + 1];
@@ -262,16 +250,16 @@ __device__ __forceinline__ double fs_scharr(const float* P) {          // P: the
     return sqrt(gx * gx + gy * gy);
 }
 
-__global__ __launch_bounds__(256) void fsim_combine_kernel(FsImgs imgs, FsMap map, int Bc, int i0, int H, int W, int ks, int h, int w, int O,
+__global__ __launch_bounds__(256) void fsim_combine_kernel(EachSets imgs, EachMap map, int Bc, int i0, int H, int W, int ks, int h, int w, int O,
                                                            const float* __restrict__ en, const float* __restrict__ san,
                                                            const double* __restrict__ T, double* __restrict__ partial) {
     constexpr int HL = FS_CT + 2;
     __shared__ float As[HL * HL], Bs[HL * HL];
     __shared__ double red[FS_SUMS * 256];
     const int k = blockIdx.z / Bc, i = blockIdx.z - k * Bc;
-    const int sa_set = pick(map, k), sb_set = map.tgt;
-    const float* __restrict__ a = pick(imgs, sa_set) + (long long)(i0 + i) * H * W;
-    const float* __restrict__ b = pick(imgs, sb_set) + (long long)(i0 + i) * H * W;
+    const int sa_set = each_pick(map, k), sb_set = map.tgt;
+    const float* __restrict__ a = each_pick(imgs, sa_set) + (long long)(i0 + i) * H * W;
+    const float* __restrict__ b = each_pick(imgs, sb_set) + (long long)(i0 + i) * H * W;
     const long long sa = (long long)sa_set * Bc + i, sb = (long long)sb_set * Bc + i;
     const int tx0 = blockIdx.x * FS_CT, ty0 = blockIdx.y * FS_CT;
     for (int e = threadIdx.x; e < HL * HL; e += 256) {
@@ -290,36 +278,27 @@ __global__ __launch_bounds__(256) void fsim_combine_kernel(FsImgs imgs, FsMap ma
     const long long hw = (long long)h * w, pix = (long long)(ty0 + ly) * w + tx0 + lx;
     const double pa = fs_pc(en, san, T, sa, O, hw, pix), pb = fs_pc(en, san, T, sb, O, hw, pix);
     const double ga = fs_scharr(As + (ly + 1) * HL + lx + 1), gb = fs_scharr(Bs + (ly + 1) * HL + lx + 1);
-    const double PC = fs_similarity(pa, pb, 0.85), GM = fs_similarity(ga, gb, 160.0);
+    const double PC = each_similarity(pa, pb, 0.85), GM = each_similarity(ga, gb, 160.0);
     const double pm = pa > pb ? pa : pb;
     double sums[FS_SUMS] = {GM * PC * pm, pm, pa, ga};
     block_sum256(sums, red);
-    if (threadIdx.x == 0) {
-        const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-#pragma unroll
-        for (int q = 0; q < FS_SUMS; ++q) partial[FS_SUMS * blk + q] = sums[q];
-    }
+    each_store(partial, sums);
 }
 
 // ---- 7. one workgroup per (source, image of the chunk) g: the tile partials in a fixed order, then score = num / den.
-__global__ __launch_bounds__(256) void fsim_finish_kernel(const double* __restrict__ partial, int tiles, FsMap map, int Bc, int i0, int B, int O,
+__global__ __launch_bounds__(256) void fsim_finish_kernel(const double* __restrict__ partial, int tiles, EachMap map, int Bc, int i0, int B, int O,
                                                           const double* __restrict__ T, double* __restrict__ out, double* __restrict__ parts) {
     __shared__ double red[FS_SUMS * 256];
     const int g = blockIdx.x, k = g / Bc, i = g - k * Bc;
-    const double* p = partial + (long long)FS_SUMS * g * tiles;
-    double sums[FS_SUMS] = {0.0, 0.0, 0.0, 0.0};
-    for (int t = threadIdx.x; t < tiles; t += 256) {
-#pragma unroll
-        for (int q = 0; q < FS_SUMS; ++q) sums[q] += p[FS_SUMS * t + q];
-    }
-    block_sum256(sums, red);
+    double sums[FS_SUMS];
+    each_fold(partial + (long long)FS_SUMS * g * tiles, tiles, sums, red);
     if (threadIdx.x != 0) return;
     const long long at = (long long)k * B + i0 + i;
     if (parts) {
         double* pp = parts + at * (FS_SUMS + O);
 #pragma unroll
         for (int q = 0; q < FS_SUMS; ++q) pp[q] = sums[q];
-        const long long slot = (long long)pick(map, k) * Bc + i;
+        const long long slot = (long long)each_pick(map, k) * Bc + i;
         for (int o = 0; o < O; ++o) pp[FS_SUMS + o] = T[slot * O + o];
     }
     out[at] = sums[0] / sums[1];
@@ -357,10 +336,7 @@ FsPlan fsim_plan(int na, int B, int h, int w, int S, int O) {
         if (per_image <= FS_WS_TARGET || Og == 1) break;
     }
     p.Og = Og;
-    long long Bc = FS_WS_TARGET / per_image;
-    Bc = Bc < 1 ? 1 : (Bc > B ? B : Bc);
-    if (Bc > 8192) Bc = 8192;                 // (sets * Bc and na * Bc index a grid dimension)
-    p.Bc = (int)Bc;
+    const long long Bc = p.Bc = each_chunk(FS_WS_TARGET, per_image, B);
     const long long slots = sets * Bc;
     p.spec = 0;
     p.Y = p.spec + slots * hw * 8;
@@ -395,22 +371,10 @@ extern "C" int mtd_fsim_each(const void* const* srcs, int na, const void* target
     const int h = H / ks, w = W / ks, S = scales, O = orientations;
     const FsPlan p = fsim_plan(na, B, h, w, S, O);
     if (!p.ok) return MTD_EINVAL;
-    FsImgs imgs = {};
-    FsMap map = {};
-    int sets = 0;
-    imgs.p[sets] = (const float*)target;
-    map.tgt = sets++;
-    for (int a = 0; a < na; ++a) {
-        if (!srcs[a]) return MTD_EINVAL;
-        int at = -1;
-        for (int d = 0; d < sets; ++d)
-            if (imgs.p[d] == (const float*)srcs[a]) at = d;
-        if (at < 0) {
-            imgs.p[sets] = (const float*)srcs[a];
-            at = sets++;
-        }
-        map.src[a] = at;
-    }
+    EachSets imgs;
+    EachMap map;
+    const int sets = each_sets(srcs, na, target, imgs, map);
+    if (sets < 0) return MTD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)ws;
     float2* spec = (float2*)(base + p.spec);

@@ -11,7 +11,7 @@
 //     (k = 2, 4, 8, two orientations) come from it.  With subsample the halo is pooled on the way in from the 2 x 2 source
 //     pixels: the subsampled image is never stored.
 // Launches per batch: 1 tiles + 1 finish, for all na * B pairs.
-#include "common.h"
+#include "each_metric.h"
 #include <float.h>
 #include <math.h>
 
@@ -21,10 +21,6 @@ constexpr int HT = 32;                        // output tile
 constexpr int HB = 3, HA = 4;                 // halo before (above / left) and after (below / right)
 constexpr int HL = HT + HB + HA;              // 39
 constexpr int HP_PARTS = 4;                   // (num, den) of the filter as it is, then of its transpose
-
-struct HpSlots { const float* p[3]; };        // the sources, B images each
-
-__device__ __forceinline__ const float* pick(const HpSlots& s, int k) { return k == 0 ? s.p[0] : (k == 1 ? s.p[1] : s.p[2]); }
 
 // Pixel (y, x) of the map the filters see: 255 * image, with SUB after piq's zero padding at the bottom and the right by
 // max(H % 2, W % 2) and its 2 x 2 average pool.  0 <= y < h, 0 <= x < w; then 2y < H and 2x < W, and only row 2y + 1 or column
@@ -73,14 +69,13 @@ __device__ __forceinline__ void hp_coefficients(const float* P, float (&cf)[6]) 
 // grid (tiles of w, tiles of h, na * B); blockIdx.z = source * B + image.  The four sums of the tile go to partial[4 blk], blk
 // the linear workgroup index, so the partials of one (source, image) are contiguous.
 template <bool SUB>
-__global__ __launch_bounds__(256) void haarpsi_tiles_kernel(HpSlots src, const float* __restrict__ b, int B, int H, int W, int h, int w,
+__global__ __launch_bounds__(256) void haarpsi_tiles_kernel(EachSets src, const float* __restrict__ b, int B, int H, int W, int h, int w,
                                                             float c, float alpha, double* __restrict__ partial) {
     __shared__ float As[HL * HL], Bs[HL * HL];
     __shared__ double red[HP_PARTS * 256];
     const int si = blockIdx.z / B, i = blockIdx.z - si * B;
-    const float* __restrict__ a = pick(src, si) + (long long)i * H * W;
+    const float* __restrict__ a = each_pick(src, si) + (long long)i * H * W;
     const float* __restrict__ bi = b + (long long)i * H * W;
-    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     const int tid = threadIdx.x;
     const int tx0 = blockIdx.x * HT, ty0 = blockIdx.y * HT;
     for (int e = tid; e < HL * HL; e += 256) {
@@ -120,10 +115,7 @@ __global__ __launch_bounds__(256) void haarpsi_tiles_kernel(HpSlots src, const f
         }
     }
     block_sum256(sums, red);
-    if (tid == 0) {
-#pragma unroll
-        for (int q = 0; q < HP_PARTS; ++q) partial[HP_PARTS * blk + q] = sums[q];
-    }
+    each_store(partial, sums);
 }
 
 // One workgroup per (source, image) g: the image's tile partials in a fixed order (thread t takes tiles t, t + 256, ..., then
@@ -132,13 +124,8 @@ __global__ __launch_bounds__(256) void haarpsi_finish_kernel(const double* __res
                                                              double* __restrict__ out, double* __restrict__ parts) {
     __shared__ double red[HP_PARTS * 256];
     const int g = blockIdx.x;
-    const double* p = partial + (long long)HP_PARTS * g * tiles;
-    double sums[HP_PARTS] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < tiles; i += 256) {
-#pragma unroll
-        for (int q = 0; q < HP_PARTS; ++q) sums[q] += p[HP_PARTS * i + q];
-    }
-    block_sum256(sums, red);
+    double sums[HP_PARTS];
+    each_fold(partial + (long long)HP_PARTS * g * tiles, tiles, sums, red);
     if (threadIdx.x != 0) return;
     if (parts) {
 #pragma unroll
@@ -184,7 +171,7 @@ extern "C" int mtd_haarpsi_each(const float* const a[3], int na, const float* b,
     if (!a || !b || !out || !ws || !(c > 0.f) || !(alpha > 0.f)) return MTD_EINVAL;
     const HpPlan p = haarpsi_plan(na, B, H, W, subsample);
     if (!p.ok) return MTD_EINVAL;
-    HpSlots src = {};
+    EachSets src = {};                           // the sources
     for (int k = 0; k < na; ++k) {
         if (!a[k]) return MTD_EINVAL;
         src.p[k] = a[k];

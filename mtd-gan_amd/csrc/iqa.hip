@@ -8,7 +8,7 @@
 //     applies the N-tap Gaussian separably to the five moment maps a, b, a^2, b^2, ab, as image_metrics_each_kernel does;
 //   * the pyramids (MS-SSIM: four 2 x 2 average pools; VIFp: three filtered and subsampled levels) live in the caller's workspace.
 // Launches per batch: MS-SSIM 1 pyramid + 5 levels + 1 finish, VIFp 3 levels down + 4 scales + 1 finish, GMSD 1 + 1 finish.
-#include "common.h"
+#include "each_metric.h"
 #include <math.h>
 
 namespace {
@@ -18,9 +18,6 @@ constexpr int MS_LEVELS = 5, MS_WIN = 11, VIF_SCALES = 4;
 constexpr int PARTS = 20;                     // stage values per (source, image): 10 MS-SSIM, 8 VIFp, 2 GMSD
 
 struct IqaWeights { float w[17]; };           // the 1-D window (by value: its reads are unrolled, the weights stay in scalar registers)
-struct IqaSlots { const float* p[4]; };       // B images each: the sources, and for the pyramid kernels the target in slot na
-
-__device__ __forceinline__ const float* pick(const IqaSlots& s, int k) { return k == 0 ? s.p[0] : (k == 1 ? s.p[1] : (k == 2 ? s.p[2] : s.p[3])); }
 
 // ------------------------------------------------------------------------------------------------ MS-SSIM pyramid
 // Level l (1..4) of piq's pyramid: replicate-pad level l-1 on the left and top by p[l] = max(h % 2, w % 2) of level l-1, then a
@@ -46,14 +43,14 @@ __device__ __forceinline__ float ms_pool(const float* __restrict__ img, const Ms
 }
 
 // grid (pixels of level 1 / 256, 4 levels, (na + 1) * B images); ws level l holds image z at off[l] + z * h[l] * w[l]
-__global__ __launch_bounds__(256) void ms_pyramid_kernel(IqaSlots src, int B, MsDims d, float* __restrict__ ws) {
+__global__ __launch_bounds__(256) void ms_pyramid_kernel(EachSets src, int B, MsDims d, float* __restrict__ ws) {
     const int l = blockIdx.y + 1;
     const int z = blockIdx.z, slot = z / B, i = z - slot * B;
     const int hw = d.h[l] * d.w[l];
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= hw) return;
     const int y = e / d.w[l], x = e - y * d.w[l];
-    const float* img = pick(src, slot) + (long long)i * d.h[0] * d.w[0];
+    const float* img = each_pick(src, slot) + (long long)i * d.h[0] * d.w[0];
     float v;
     if (l == 1) v = ms_pool<1>(img, d, y, x);
     else if (l == 2) v = ms_pool<2>(img, d, y, x);
@@ -66,12 +63,12 @@ __global__ __launch_bounds__(256) void ms_pyramid_kernel(IqaSlots src, int B, Ms
 // Scale s > 1 of vif_p: the valid N x N Gaussian of that scale on the level before, every second row and column kept.
 // out (slots * B, oh, ow), oh = (h - N + 2) / 2.  A thread per output; the taps come through the caches.
 template <int N>
-__global__ __launch_bounds__(256) void vif_down_kernel(IqaSlots src, int B, int h, int w, IqaWeights wt, float* __restrict__ out, int oh, int ow) {
+__global__ __launch_bounds__(256) void vif_down_kernel(EachSets src, int B, int h, int w, IqaWeights wt, float* __restrict__ out, int oh, int ow) {
     const int z = blockIdx.z, slot = z / B, i = z - slot * B;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= oh * ow) return;
     const int y = e / ow, x = e - y * ow;
-    const float* img = pick(src, slot) + (long long)i * h * w + (long long)(2 * y) * w + 2 * x;      // rows 2y .. 2y + N - 1 <= h - 1
+    const float* img = each_pick(src, slot) + (long long)i * h * w + (long long)(2 * y) * w + 2 * x;      // rows 2y .. 2y + N - 1 <= h - 1
     float acc = 0.f;
 #pragma unroll
     for (int r = 0; r < N; ++r) {
@@ -91,16 +88,15 @@ enum { IQA_SSIM = 0, IQA_VIF = 1 };
 // of valid N x N windows.  blockIdx.z = source * B + image; the two sums go to partial[2 blk], blk the linear workgroup index,
 // so the partials of one (source, image) are contiguous.
 template <int N, int MODE>
-__global__ __launch_bounds__(256) void iqa_moments_kernel(IqaSlots src, const float* __restrict__ b, int B, int h, int w, IqaWeights wt,
+__global__ __launch_bounds__(256) void iqa_moments_kernel(EachSets src, const float* __restrict__ b, int B, int h, int w, IqaWeights wt,
                                                           float sigma_n, double* __restrict__ partial) {
     constexpr int HL = IT + N - 1;
     __shared__ float As[HL * HL], Bs[HL * HL];
     __shared__ float Hs[5][HL * IT];
     __shared__ double red[2 * 256];
     const int si = blockIdx.z / B, i = blockIdx.z - si * B;
-    const float* __restrict__ a = pick(src, si);
+    const float* __restrict__ a = each_pick(src, si);
     const long long img = (long long)i * h * w;
-    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     const int tid = threadIdx.x;
     const int tx0 = blockIdx.x * IT, ty0 = blockIdx.y * IT;
     const int oh = h - N + 1, ow = w - N + 1;
@@ -170,10 +166,7 @@ __global__ __launch_bounds__(256) void iqa_moments_kernel(IqaSlots src, const fl
     }
     double sums[2] = {s0, s1};
     block_sum256(sums, red);
-    if (tid == 0) {
-        partial[2 * blk] = sums[0];
-        partial[2 * blk + 1] = sums[1];
-    }
+    each_store(partial, sums);
 }
 
 // ------------------------------------------------------------------------------------------------ GMSD
@@ -191,15 +184,14 @@ __device__ __forceinline__ float pooled(const float* __restrict__ img, int H, in
     return 0.25f * s;
 }
 
-__global__ __launch_bounds__(256) void gmsd_kernel(IqaSlots src, const float* __restrict__ b, int B, int H, int W, int hp, int wp,
+__global__ __launch_bounds__(256) void gmsd_kernel(EachSets src, const float* __restrict__ b, int B, int H, int W, int hp, int wp,
                                                    double* __restrict__ partial) {
     constexpr int PL = IT + 2;
     __shared__ float Pa[PL * PL], Pb[PL * PL];
     __shared__ double red[2 * 256];
     const int si = blockIdx.z / B, i = blockIdx.z - si * B;
-    const float* __restrict__ a = pick(src, si) + (long long)i * H * W;
+    const float* __restrict__ a = each_pick(src, si) + (long long)i * H * W;
     const float* __restrict__ bi = b + (long long)i * H * W;
-    const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     const int tid = threadIdx.x;
     const int tx0 = blockIdx.x * IT, ty0 = blockIdx.y * IT;
     for (int e = tid; e < PL * PL; e += 256) {
@@ -243,10 +235,7 @@ __global__ __launch_bounds__(256) void gmsd_kernel(IqaSlots src, const float* __
     }
     double sums[2] = {s0, s1};
     block_sum256(sums, red);
-    if (tid == 0) {
-        partial[2 * blk] = sums[0];
-        partial[2 * blk + 1] = sums[1];
-    }
+    each_store(partial, sums);
 }
 
 // ------------------------------------------------------------------------------------------------ finish
@@ -265,10 +254,8 @@ __global__ __launch_bounds__(256) void iqa_finish_kernel(const double* __restric
     const int g = blockIdx.x;
     double st[MS_LEVELS][2];
     for (int s = 0; s < f.stages; ++s) {
-        const double* p = partial + f.off[s] + 2LL * g * f.tiles[s];
-        double sums[2] = {0.0, 0.0};
-        for (int i = threadIdx.x; i < f.tiles[s]; i += 256) { sums[0] += p[2 * i]; sums[1] += p[2 * i + 1]; }
-        block_sum256(sums, red);
+        double sums[2];
+        each_fold(partial + f.off[s] + 2LL * g * f.tiles[s], f.tiles[s], sums, red);
         st[s][0] = sums[0];
         st[s][1] = sums[1];
         __syncthreads();
@@ -375,14 +362,14 @@ IqaPlan iqa_plan(int mask, int na, int B, int H, int W) {
 }
 
 // the B-image blocks of the slots of a workspace level
-IqaSlots level_slots(const float* base, int slots, long long per_slot) {
-    IqaSlots s = {};
+EachSets level_slots(const float* base, int slots, long long per_slot) {
+    EachSets s = {};
     for (int k = 0; k < slots; ++k) s.p[k] = base + k * per_slot;
     return s;
 }
 
 template <int N, int MODE>
-int moments_launch(const IqaSlots& a, const float* b, int na, int B, int h, int w, const IqaWeights& wt, float sigma_n, double* partial,
+int moments_launch(const EachSets& a, const float* b, int na, int B, int h, int w, const IqaWeights& wt, float sigma_n, double* partial,
                    hipStream_t s) {
     const dim3 grid((w - N + 1 + IT - 1) / IT, (h - N + 1 + IT - 1) / IT, na * B);
     hipLaunchKernelGGL((iqa_moments_kernel<N, MODE>), grid, dim3(256), 0, s, a, b, B, h, w, wt, sigma_n, partial);
@@ -391,7 +378,7 @@ int moments_launch(const IqaSlots& a, const float* b, int na, int B, int h, int 
 }
 
 template <int N>
-int down_launch(const IqaSlots& in, int slots, int B, int h, int w, const IqaWeights& wt, float* out, int oh, int ow, hipStream_t s) {
+int down_launch(const EachSets& in, int slots, int B, int h, int w, const IqaWeights& wt, float* out, int oh, int ow, hipStream_t s) {
     const dim3 grid((oh * ow + 255) / 256, 1, slots * B);
     hipLaunchKernelGGL((vif_down_kernel<N>), grid, dim3(256), 0, s, in, B, h, w, wt, out, oh, ow);
     MTD_LAUNCH_CHECK();
@@ -417,7 +404,7 @@ extern "C" int mtd_iqa_each(const float* const a[3], int na, const float* b, int
     double* dws = (double*)ws;
     float* fws = (float*)(dws + p.doubles);
     const int nimg = na * B;
-    IqaSlots src = {}, all = {};               // the sources; the sources and the target behind them
+    EachSets src = {}, all = {};               // the sources; the sources and the target behind them
     for (int k = 0; k < na; ++k) src.p[k] = all.p[k] = a[k];
     all.p[na] = b;
     int row = 0, rc;
@@ -431,7 +418,7 @@ extern "C" int mtd_iqa_each(const float* const a[3], int na, const float* b, int
         f.stages = MS_LEVELS;
         for (int l = 0; l < MS_LEVELS; ++l) {
             const long long per_slot = (long long)B * d.h[l] * d.w[l];
-            const IqaSlots lv = l == 0 ? src : level_slots(fws + d.off[l], na, per_slot);
+            const EachSets lv = l == 0 ? src : level_slots(fws + d.off[l], na, per_slot);
             const float* tb = l == 0 ? b : fws + d.off[l] + na * per_slot;
             if ((rc = moments_launch<MS_WIN, IQA_SSIM>(lv, tb, na, B, d.h[l], d.w[l], wt, 0.f, dws + p.ms_part[l], s)) != MTD_OK) return rc;
             f.off[l] = p.ms_part[l];
@@ -451,7 +438,7 @@ extern "C" int mtd_iqa_each(const float* const a[3], int na, const float* b, int
             const IqaWeights wt = gaussian(n, n / 5.0);
             if (sc > 0) {
                 const int ph = p.vh[sc - 1], pw = p.vw[sc - 1];
-                const IqaSlots in = sc == 1 ? all : level_slots(fws + p.voff[sc - 1], na + 1, (long long)B * ph * pw);
+                const EachSets in = sc == 1 ? all : level_slots(fws + p.voff[sc - 1], na + 1, (long long)B * ph * pw);
                 float* o = fws + p.voff[sc];
                 rc = sc == 1 ? down_launch<9>(in, na + 1, B, ph, pw, wt, o, h, w, s)
                    : sc == 2 ? down_launch<5>(in, na + 1, B, ph, pw, wt, o, h, w, s)
@@ -459,7 +446,7 @@ extern "C" int mtd_iqa_each(const float* const a[3], int na, const float* b, int
                 if (rc != MTD_OK) return rc;
             }
             const long long per_slot = (long long)B * h * w;
-            const IqaSlots lv = sc == 0 ? src : level_slots(fws + p.voff[sc], na, per_slot);
+            const EachSets lv = sc == 0 ? src : level_slots(fws + p.voff[sc], na, per_slot);
             const float* tb = sc == 0 ? b : fws + p.voff[sc] + na * per_slot;
             double* part = dws + p.vif_part[sc];
             rc = sc == 0 ? moments_launch<17, IQA_VIF>(lv, tb, na, B, h, w, wt, sigma_n_sq, part, s)

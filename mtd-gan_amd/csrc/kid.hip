@@ -22,11 +22,9 @@
 //   kid_mean_kernel        the means over the subsets, in subset order.
 // No floating-point atomics anywhere: a second call gives the same bits, and a subset's values depend neither on its place
 // among the S subsets nor on S.
-#include "common.h"
+#include "gram64.h"          // f64x4, gram64_fetch
 
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KT = 64;                  // tile side
 constexpr int KK = 16;                  // k per stage
@@ -47,17 +45,6 @@ struct KidArgs {
 };
 
 inline long long kid_tiles(int m) { return (m + KT - 1) / KT; }
-
-// four consecutive k of one feature row, as stored; row < 0: zeros
-__device__ __forceinline__ void kid_fetch(const float* __restrict__ F, int row, int D, int kb, bool vec, float (&r)[4]) {
-    if (row >= 0 && vec && kb + 3 < D) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(F + (long long)row * D + kb);
-        r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = v[3];
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) r[q] = (row >= 0 && kb + q < D) ? F[(long long)row * D + kb + q] : 0.f;
-    }
-}
 
 __global__ __launch_bounds__(256) void kid_gram_sums_kernel(KidArgs a) {
     __shared__ double As[KK][KLD];
@@ -92,8 +79,8 @@ __global__ __launch_bounds__(256) void kid_gram_sums_kernel(KidArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
     float ra[4], rb[4];
-    kid_fetch(FA, rowa, a.D, kq, veca, ra);
-    kid_fetch(FB, rowb, a.D, kq, vecb, rb);
+    gram64_fetch(FA, rowa, a.D, kq, veca, ra);
+    gram64_fetch(FB, rowb, a.D, kq, vecb, rb);
     for (int k0 = 0; k0 < a.D; k0 += KK) {
         __syncthreads();                               // the stage before has been read
 #pragma unroll
@@ -103,8 +90,8 @@ __global__ __launch_bounds__(256) void kid_gram_sums_kernel(KidArgs a) {
         }
         __syncthreads();
         if (k0 + KK < a.D) {
-            kid_fetch(FA, rowa, a.D, k0 + KK + kq, veca, ra);
-            kid_fetch(FB, rowb, a.D, k0 + KK + kq, vecb, rb);
+            gram64_fetch(FA, rowa, a.D, k0 + KK + kq, veca, ra);
+            gram64_fetch(FB, rowb, a.D, k0 + KK + kq, vecb, rb);
         }
 #pragma unroll
         for (int kk = 0; kk < KK; kk += 4) {

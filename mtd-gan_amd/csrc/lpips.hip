@@ -15,7 +15,7 @@
 //   channel_moments_kernel   threads own a float4 of channels (or the one channel of a C = 1 map) and walk the pixels of the
 //                            workgroup's range with a stride of PL = 256 / (C / 4) pixels; the PL pixel lanes meet in LDS.
 //   *_finish_kernel          the fixed-order sums of the partials; dists_finish_kernel is the closing formula of DISTS.
-#include "common.h"
+#include "each_metric.h"     // each_fold
 
 // No contraction of a * b - c into an fma: a map against itself must give exactly 0 (LPIPS) and exactly S = 1 (DISTS), which holds
 // when both sides of a difference are rounded alike.  The fused forms that are wanted are written as fma / fmaf below.
@@ -139,11 +139,9 @@ __global__ __launch_bounds__(256) void lpips_level_finish_kernel(const double* _
                                                                  long long out_stride, long long other_stride) {
     __shared__ double red[256];
     const int i = blockIdx.x, k = blockIdx.y;
-    const double* p = partial + ((long long)k * B + i) * nblk;
-    double s = 0.0;
-    for (int j = threadIdx.x; j < nblk; j += 256) s += p[j];
-    s = block_sum256(s, red);
-    if (threadIdx.x == 0) out[k * other_stride + i * out_stride] = s;
+    double s[1];
+    each_fold(partial + ((long long)k * B + i) * nblk, nblk, s, red);
+    if (threadIdx.x == 0) out[k * other_stride + i * out_stride] = s[0];
 }
 
 int lpips_blocks(int hw, int C) {

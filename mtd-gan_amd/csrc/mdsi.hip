@@ -10,7 +10,7 @@
 //   * the expressions are grouped so that an image against itself gives z = 1 at every pixel exactly, hence a mean of exactly 1
 //     and a score of exactly 0.
 // Launches per chunk of the batch: tiles (pass one), finish (means), tiles (pass two), finish (scores).
-#include "common.h"
+#include "each_metric.h"
 #include <float.h>
 #include <math.h>
 
@@ -23,10 +23,7 @@ constexpr int MD_HL = MD_CT + 2;
 constexpr int MD_MIN_N = MTD_MDSI_MIN_SIDE, MD_MAX_N = MTD_MDSI_MAX_SIDE;
 constexpr long long MD_WS_TARGET = 16LL << 20;
 
-struct MdImgs { const float* p[3]; const float* tgt; };
 struct MdOpts { double c1, c2, c3, alpha, beta, gamma, rho, q, o; int mult; };
-
-__device__ __forceinline__ const float* pick(const MdImgs& s, int k) { return k == 0 ? s.p[0] : (k == 1 ? s.p[1] : s.p[2]); }
 
 // Pixel (y, x) of the pooled map of 255 * image: piq pads [(k - 1) / 2, k / 2] ZEROS on each axis (k >= 2), then avg_pool2d with
 // kernel and stride k (floor; the padding counts in the divisor).  0 <= y < (H + k - 1) / k, likewise x.
@@ -40,11 +37,6 @@ __device__ __forceinline__ double md_pixel(const float* __restrict__ img, int H,
             if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) s += 255.0 * (double)img[(long long)yy * W + xx];
         }
     return s / (double)(k * k);
-}
-
-// piq's similarity_map.  Equal maps give a ratio of exactly 1 (no contraction in this file).
-__device__ __forceinline__ double md_similarity(double a, double b, double c) {
-    return (2.0 * a * b + c) / (a * a + b * b + c);
 }
 
 // Prewitt magnitude at the centre of a 3 x 3 neighbourhood of the 18-wide halo tile (zero padding is in the tile).  piq's
@@ -66,7 +58,7 @@ __device__ __forceinline__ MdZ md_real_pow(double base, double e) {
 
 // z = gcs^q at a pooled pixel from the three gradient magnitudes and the chromaticity channels.
 __device__ __forceinline__ MdZ md_z(double ga, double gb, double gavg, double Ha, double Hb, double Ma, double Mb, const MdOpts& o) {
-    const double gs = md_similarity(ga, gb, o.c1) + md_similarity(ga, gavg, o.c2) - md_similarity(gb, gavg, o.c2);
+    const double gs = each_similarity(ga, gb, o.c1) + each_similarity(ga, gavg, o.c2) - each_similarity(gb, gavg, o.c2);
     const double cs = (2.0 * (Ha * Hb + Ma * Mb) + o.c3) / ((Ha * Ha + Hb * Hb) + (Ma * Ma + Mb * Mb) + o.c3);
     if (!o.mult) return md_real_pow(o.alpha * gs + (1.0 - o.alpha) * cs, o.q);
     const MdZ g = md_real_pow(gs, o.gamma), c = md_real_pow(cs, o.beta);
@@ -78,13 +70,13 @@ __device__ __forceinline__ MdZ md_z(double ga, double gb, double gavg, double Ha
 // grid (ceil(wp / 16), ceil(hp / 16), na * Bc); blockIdx.z = source * Bc + image of the chunk.  PASS 1: the tile's sums of
 // re z and im z -> partial[2 * blk ..]; PASS 2: its sum of |z - mean|^rho -> partial[blk].
 template <int PASS>
-__global__ __launch_bounds__(256) void mdsi_tile_kernel(MdImgs imgs, int Bc, int i0, int H, int W, int k, int hp, int wp, MdOpts o,
+__global__ __launch_bounds__(256) void mdsi_tile_kernel(EachSets imgs, int Bc, int i0, int H, int W, int k, int hp, int wp, MdOpts o,
                                                         const double* __restrict__ mean, double* __restrict__ partial) {
     __shared__ double Pa[MD_HL * MD_HL], Pb[MD_HL * MD_HL], La[MD_HL * MD_HL], Lb[MD_HL * MD_HL];
     __shared__ double red[2 * 256];
     const int s = blockIdx.z / Bc, i = blockIdx.z - s * Bc;
-    const float* __restrict__ a = pick(imgs, s) + (long long)(i0 + i) * H * W;
-    const float* __restrict__ b = imgs.tgt + (long long)(i0 + i) * H * W;
+    const float* __restrict__ a = each_pick(imgs, s) + (long long)(i0 + i) * H * W;         // sets 0..2: the sources; 3: the target
+    const float* __restrict__ b = imgs.p[3] + (long long)(i0 + i) * H * W;
     const int tx0 = blockIdx.x * MD_CT, ty0 = blockIdx.y * MD_CT;
     // the row sums of piq's RGB -> LHM matrix, its entries rounded to fp32 as piq holds them, product by product
     const double l0 = (double)0.2989f, l1 = (double)0.587f, l2 = (double)0.114f;
@@ -131,14 +123,11 @@ __global__ __launch_bounds__(256) void mdsi_tile_kernel(MdImgs imgs, int Bc, int
         }
     }
     block_sum256(sums, red);
-    if (threadIdx.x == 0) {
-        const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        if (PASS == 1) {
-            partial[2 * blk] = sums[0];
-            partial[2 * blk + 1] = sums[1];
-        } else {
-            partial[blk] = sums[0];
-        }
+    if (PASS == 1) {
+        each_store(partial, sums);
+    } else {
+        const double dev[1] = {sums[0]};
+        each_store(partial, dev);
     }
 }
 
@@ -150,15 +139,10 @@ __global__ __launch_bounds__(256) void mdsi_finish_kernel(const double* __restri
     __shared__ double red[2 * 256];
     const int g = blockIdx.x, s = g / Bc, i = g - s * Bc;
     constexpr int Q = PASS == 1 ? 2 : 1;
-    const double* p = partial + (long long)Q * g * tiles;
-    double sums[2] = {0.0, 0.0};
-    for (int t = threadIdx.x; t < tiles; t += 256) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) sums[q] += p[Q * t + q];
-    }
-    block_sum256(sums, red);
+    double sums[Q];
+    each_fold(partial + (long long)Q * g * tiles, tiles, sums, red);
     if (threadIdx.x != 0) return;
-    if (PASS == 1) {
+    if constexpr (PASS == 1) {
         mean[2 * g] = sums[0] / n;
         mean[2 * g + 1] = sums[1] / n;
         return;
@@ -179,7 +163,7 @@ struct MdPlan {
 };
 
 // The workspace holds, per source and image of a chunk, two doubles per tile and the two means.  Bc is the largest count for
-// which that stays within 16 MiB, at least 1, at most B and 8192 (na * Bc indexes a grid dimension).
+// which that stays within 16 MiB (each_chunk).
 MdPlan mdsi_plan(int na, int B, int H, int W, int k) {
     MdPlan p = {};
     if (na < 1 || na > 3 || B < 1 || B > (1 << 24) || k < 1 || k > 8) return p;
@@ -188,18 +172,13 @@ MdPlan mdsi_plan(int na, int B, int H, int W, int k) {
     p.wp = (W + k - 1) / k;
     p.tiles = ((p.hp + MD_CT - 1) / MD_CT) * ((p.wp + MD_CT - 1) / MD_CT);
     const long long per_image = (long long)na * (p.tiles * 16LL + 16);
-    long long Bc = MD_WS_TARGET / per_image;
-    Bc = Bc < 1 ? 1 : (Bc > B ? B : Bc);
-    if (Bc > 8192) Bc = 8192;
-    p.Bc = (int)Bc;
+    const long long Bc = p.Bc = each_chunk(MD_WS_TARGET, per_image, B);
     p.mean = 0;
     p.partial = p.mean + (long long)na * Bc * 16;
     p.bytes = p.partial + (long long)na * Bc * p.tiles * 16;
     p.ok = true;
     return p;
 }
-
-bool md_finite(double v) { return v == v && v - v == 0.0; }
 
 }  // namespace
 
@@ -214,11 +193,11 @@ extern "C" int mtd_mdsi_each(const void* const* srcs, int na, const void* target
     const MdPlan p = mdsi_plan(na, B, H, W, k);
     if (!p.ok) return MTD_EINVAL;
     for (int j = 0; j < MTD_MDSI_OPTIONS; ++j)
-        if (!md_finite(options[j])) return MTD_EINVAL;
+        if (!each_finite(options[j])) return MTD_EINVAL;
     const MdOpts o = {options[0], options[1], options[2], options[3], options[4], options[5], options[6], options[7], options[8], mult};
     if (!(o.c1 > 0.0) || !(o.c2 > 0.0) || !(o.c3 > 0.0) || !(o.rho > 0.0)) return MTD_EINVAL;
-    MdImgs imgs = {};
-    imgs.tgt = (const float*)target;
+    EachSets imgs = {};
+    imgs.p[3] = (const float*)target;
     for (int a = 0; a < na; ++a) {
         if (!srcs[a]) return MTD_EINVAL;
         imgs.p[a] = (const float*)srcs[a];

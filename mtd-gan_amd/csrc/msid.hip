@@ -25,11 +25,9 @@
 // The distance of two descriptors: max c |dp - dt| or the l2 norm.  The Inception Score: one workgroup per split.
 // No floating-point atomics anywhere: two calls on the same inputs give the same bits.
 #include <limits.h>
-#include "common.h"
+#include "gram64.h"          // f64x4, gram64_fetch
 
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MT = 64;                  // tile side of the distance product
 constexpr int MK = 16;                  // k per stage
@@ -78,17 +76,6 @@ __global__ __launch_bounds__(256) void msid_sqnorm_kernel(const float* __restric
     if (lane == 0) dd[row] = s;
 }
 
-// four consecutive k of one feature row, as stored; row < 0: zeros
-__device__ __forceinline__ void msid_fetch(const float* __restrict__ F, int row, int D, int kb, bool vec, float (&r)[4]) {
-    if (row >= 0 && vec && kb + 3 < D) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(F + (long long)row * D + kb);
-        r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = v[3];
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) r[q] = (row >= 0 && kb + q < D) ? F[(long long)row * D + kb + q] : 0.f;
-    }
-}
-
 // dist[(i - row0) * N + j] = dd[j] - 2 Xi . Xj for row0 <= i < row0 + rows, 0 <= j < N.  grid (ceil(N / 64), ceil(rows / 64)).
 __global__ __launch_bounds__(256) void msid_dist_kernel(const float* __restrict__ X, int N, int D, const double* __restrict__ dd, int row0,
                                                         int rows, double* __restrict__ dist) {
@@ -108,8 +95,8 @@ __global__ __launch_bounds__(256) void msid_dist_kernel(const float* __restrict_
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
     float ra[4], rb[4];
-    msid_fetch(X, rowa, D, kq, vec, ra);
-    msid_fetch(X, rowb, D, kq, vec, rb);
+    gram64_fetch(X, rowa, D, kq, vec, ra);
+    gram64_fetch(X, rowb, D, kq, vec, rb);
     for (int k0 = 0; k0 < D; k0 += MK) {
         __syncthreads();                               // the stage before has been read
 #pragma unroll
@@ -119,8 +106,8 @@ __global__ __launch_bounds__(256) void msid_dist_kernel(const float* __restrict_
         }
         __syncthreads();
         if (k0 + MK < D) {
-            msid_fetch(X, rowa, D, k0 + MK + kq, vec, ra);
-            msid_fetch(X, rowb, D, k0 + MK + kq, vec, rb);
+            gram64_fetch(X, rowa, D, k0 + MK + kq, vec, ra);
+            gram64_fetch(X, rowb, D, k0 + MK + kq, vec, rb);
         }
 #pragma unroll
         for (int kk = 0; kk < MK; kk += 4) {

@@ -122,13 +122,8 @@ __global__ __launch_bounds__(256) void gram_l1_finish_kernel(const double* __res
     __shared__ double red[256];
     double s = 0.0;
     for (long long i = threadIdx.x; i < nblk; i += 256) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0];
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) out[0] = s;
 }
 
 // One workgroup per image.  The partials sit at pair * patches + patch with an image's P1 patches contiguous; image i's are
@@ -144,13 +139,8 @@ __global__ __launch_bounds__(256) void gram_l1_each_finish_kernel(const double* 
         const int pair = i / P1, q = i - pair * P1;
         s += p[(long long)pair * patches + q];
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[(long long)blockIdx.x * out_stride] = red[0];
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) out[(long long)blockIdx.x * out_stride] = s;
 }
 
 struct Scales { double s[MTD_SCALED_SUMS_MAX]; };

@@ -13,7 +13,7 @@
 //     combine stage resamples again with the same function (no contraction in this file: the same bits).
 // Launches per chunk of the batch: resample + Lab + rows forward, columns (forward, filter, inverse), rows inverse + priors,
 // minimum / maximum of the resampled map (tiles, then per image), combine, finish.
-#include "common.h"
+#include "each_metric.h"
 #include "lds_fft.h"
 #include <float.h>
 #include <math.h>
@@ -35,12 +35,7 @@ constexpr int VS_SUMS = 4;                    // num, den, sum of the source's p
 constexpr int VS_MIN_N = MTD_VSI_MIN_SIDE, VS_MAX_N = MTD_VSI_MAX_SIDE;
 constexpr long long VS_WS_TARGET = 64LL << 20;
 
-struct VsImgs { const float* p[4]; };         // the distinct image sets, B images each
-struct VsMap { int src[3]; int tgt; };        // set of source k, set of the target
 struct VsOpts { double c1, c2, c3, alpha, beta, sigma_d, sigma_c; };
-
-__device__ __forceinline__ const float* pick(const VsImgs& s, int k) { return k == 0 ? s.p[0] : (k == 1 ? s.p[1] : (k == 2 ? s.p[2] : s.p[3])); }
-__device__ __forceinline__ int pick(const VsMap& m, int k) { return k == 0 ? m.src[0] : (k == 1 ? m.src[1] : m.src[2]); }
 
 // Pixel (dy, dx) of 255 * image resampled to 256 x 256 as interpolate(mode='bilinear', align_corners=False) does it: source
 // coordinate (d + 0.5) * in / 256 - 0.5 clamped at 0, two taps per axis, no antialiasing.
@@ -99,13 +94,13 @@ __device__ __forceinline__ void vs_block_extremes(double (&v)[N], double* red) {
 
 // ---- 1. resample + Lab + forward rows of the three channels.  grid (VS_RT, sets * Bc); slot = set * Bc + image of the chunk.
 // spec: (slot, channel, 256, 256) complex; ab: (slot, 2, 256, 256) doubles; ext: (slot, VS_RT, 6) the tile's extremes.
-__global__ __launch_bounds__(256) void vsi_rows_fwd_kernel(VsImgs imgs, int Bc, int i0, int H, int W, float2* __restrict__ spec,
+__global__ __launch_bounds__(256) void vsi_rows_fwd_kernel(EachSets imgs, int Bc, int i0, int H, int W, float2* __restrict__ spec,
                                                            double* __restrict__ ab, double* __restrict__ ext) {
     __shared__ float2 buf[3 * VS_RL * VS_LD];
     __shared__ float2 tw[256];
     __shared__ double red[6 * 256];
     const int slot = blockIdx.y, set = slot / Bc, i = slot - set * Bc;
-    const float* __restrict__ img = pick(imgs, set) + (long long)(i0 + i) * H * W;
+    const float* __restrict__ img = each_pick(imgs, set) + (long long)(i0 + i) * H * W;
     const int y0 = blockIdx.x * VS_RL;
     fs_twiddles(tw, VS_N);
     double ex[6] = {DBL_MAX, -DBL_MAX, DBL_MAX, -DBL_MAX, DBL_MAX, -DBL_MAX};
@@ -295,9 +290,6 @@ __device__ __forceinline__ double vs_pooled_saliency(const double* __restrict__ 
     return s / (double)(k * k);
 }
 
-// piq's similarity_map.  Equal maps give a ratio of exactly 1 (no contraction in this file).
-__device__ __forceinline__ double vs_similarity(double a, double b, double c) { return (2.0 * a * b + c) / (a * a + b * b + c); }
-
 __device__ __forceinline__ double vs_scharr(const double* P) {         // P: the pixel in the 18-wide halo tile
     const double a = P[-VS_HL - 1], b = P[-VS_HL], c = P[-VS_HL + 1], d = P[-1], f = P[1], g = P[VS_HL - 1], hh = P[VS_HL], i = P[VS_HL + 1];
     const double gx = (3.0 * (c - a) + 10.0 * (f - d) + 3.0 * (i - g)) / 16.0;
@@ -306,15 +298,15 @@ __device__ __forceinline__ double vs_scharr(const double* P) {         // P: the
 }
 
 // ---- 5. combine.  grid (ceil(wp / 16), ceil(hp / 16), na * Bc); blockIdx.z = source * Bc + image of the chunk.
-__global__ __launch_bounds__(256) void vsi_combine_kernel(VsImgs imgs, VsMap map, int Bc, int i0, int H, int W, int k, int hp, int wp, VsOpts o,
+__global__ __launch_bounds__(256) void vsi_combine_kernel(EachSets imgs, EachMap map, int Bc, int i0, int H, int W, int k, int hp, int wp, VsOpts o,
                                                           const double* __restrict__ vsm, const double* __restrict__ lim2,
                                                           double* __restrict__ partial) {
     __shared__ double Pa[VS_HL * VS_HL], Pb[VS_HL * VS_HL], La[VS_HL * VS_HL], Lb[VS_HL * VS_HL];
     __shared__ double red[VS_SUMS * 256];
     const int s = blockIdx.z / Bc, i = blockIdx.z - s * Bc;
-    const int sa_set = pick(map, s), sb_set = map.tgt;
-    const float* __restrict__ a = pick(imgs, sa_set) + (long long)(i0 + i) * H * W;
-    const float* __restrict__ b = pick(imgs, sb_set) + (long long)(i0 + i) * H * W;
+    const int sa_set = each_pick(map, s), sb_set = map.tgt;
+    const float* __restrict__ a = each_pick(imgs, sa_set) + (long long)(i0 + i) * H * W;
+    const float* __restrict__ b = each_pick(imgs, sb_set) + (long long)(i0 + i) * H * W;
     const long long sa = (long long)sa_set * Bc + i, sb = (long long)sb_set * Bc + i;
     const int tx0 = blockIdx.x * VS_CT, ty0 = blockIdx.y * VS_CT;
     // the row sums of piq's RGB -> LMN matrix, its entries rounded to fp32 as piq holds them, product by product
@@ -343,9 +335,9 @@ __global__ __launch_bounds__(256) void vsi_combine_kernel(VsImgs imgs, VsMap map
         const double vb = vs_pooled_saliency(vsm + sb * VS_NN, lim2[2 * sb], lim2[2 * sb + 1], H, W, k, ty0 + ly, tx0 + lx);
         const double ga = vs_scharr(La + c), gb = vs_scharr(Lb + c);
         const double pa = Pa[c], pb = Pb[c];
-        const double s_vs = vs_similarity(va, vb, o.c1), s_gm = vs_similarity(ga, gb, o.c2);
-        const double s_m = vs_similarity(pa * m0 + pa * m1 + pa * m2, pb * m0 + pb * m1 + pb * m2, o.c3);
-        const double s_n = vs_similarity(pa * n0 + pa * n1 + pa * n2, pb * n0 + pb * n1 + pb * n2, o.c3);
+        const double s_vs = each_similarity(va, vb, o.c1), s_gm = each_similarity(ga, gb, o.c2);
+        const double s_m = each_similarity(pa * m0 + pa * m1 + pa * m2, pb * m0 + pb * m1 + pb * m2, o.c3);
+        const double s_n = each_similarity(pa * n0 + pa * n1 + pa * n2, pb * n0 + pb * n1 + pb * n2, o.c3);
         const double s_c = s_m * s_n;
         const double s_c_pow = pow(fabs(s_c), o.beta) * cos(o.beta * atan2(0.0, s_c));          // the real part of the complex power
         const double vm = va > vb ? va : vb;
@@ -355,25 +347,16 @@ __global__ __launch_bounds__(256) void vsi_combine_kernel(VsImgs imgs, VsMap map
         sums[3] = ga;
     }
     block_sum256(sums, red);
-    if (threadIdx.x == 0) {
-        const long long blk = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-#pragma unroll
-        for (int q = 0; q < VS_SUMS; ++q) partial[VS_SUMS * blk + q] = sums[q];
-    }
+    each_store(partial, sums);
 }
 
 // ---- 6. one workgroup per (source, image of the chunk) g: the tile partials in a fixed order, then (num + eps) / (den + eps).
-__global__ __launch_bounds__(256) void vsi_finish_kernel(const double* __restrict__ partial, int tiles, VsMap map, int Bc, int i0, int B,
+__global__ __launch_bounds__(256) void vsi_finish_kernel(const double* __restrict__ partial, int tiles, EachMap map, int Bc, int i0, int B,
                                                          const double* __restrict__ lim2, double* __restrict__ out, double* __restrict__ parts) {
     __shared__ double red[VS_SUMS * 256];
     const int g = blockIdx.x, s = g / Bc, i = g - s * Bc;
-    const double* p = partial + (long long)VS_SUMS * g * tiles;
-    double sums[VS_SUMS] = {0.0, 0.0, 0.0, 0.0};
-    for (int t = threadIdx.x; t < tiles; t += 256) {
-#pragma unroll
-        for (int q = 0; q < VS_SUMS; ++q) sums[q] += p[VS_SUMS * t + q];
-    }
-    block_sum256(sums, red);
+    double sums[VS_SUMS];
+    each_fold(partial + (long long)VS_SUMS * g * tiles, tiles, sums, red);
     if (threadIdx.x != 0) return;
     const long long at = (long long)s * B + i0 + i;
     const double eps = (double)FLT_EPSILON;
@@ -381,7 +364,7 @@ __global__ __launch_bounds__(256) void vsi_finish_kernel(const double* __restric
         double* pp = parts + at * MTD_VSI_PARTS;
 #pragma unroll
         for (int q = 0; q < VS_SUMS; ++q) pp[q] = sums[q];
-        const long long slot = (long long)pick(map, s) * Bc + i;
+        const long long slot = (long long)each_pick(map, s) * Bc + i;
         pp[VS_SUMS] = lim2[2 * slot];
         pp[VS_SUMS + 1] = lim2[2 * slot + 1];
     }
@@ -397,7 +380,7 @@ struct VsPlan {
 // The workspace holds one chunk of Bc images of every set (na sources + the target: the pointers may all differ).  Per image of
 // a chunk and set: the three spectra (24 * 65536 bytes), a and b (16 * 65536), vs_m (8 * 65536), the extremes of the row tiles
 // and of the resampled blocks, the two limits; per image and source the tile partials.  Bc is the largest count for which that
-// stays within 64 MiB, at least 1, at most B and 8192 (sets * Bc and na * Bc index a grid dimension).
+// stays within 64 MiB (each_chunk).
 VsPlan vsi_plan(int na, int B, int H, int W, int k) {
     VsPlan p = {};
     if (na < 1 || na > 3 || B < 1 || B > (1 << 24) || k < 1 || k > 8) return p;
@@ -409,10 +392,7 @@ VsPlan vsi_plan(int na, int B, int H, int W, int k) {
     const long long sets = na + 1;
     const long long per_slot = 48LL * VS_NN + VS_RT * 48LL + p.blocks * 16LL + 16;
     const long long per_image = sets * per_slot + (long long)na * p.tiles * VS_SUMS * 8;
-    long long Bc = VS_WS_TARGET / per_image;
-    Bc = Bc < 1 ? 1 : (Bc > B ? B : Bc);
-    if (Bc > 8192) Bc = 8192;
-    p.Bc = (int)Bc;
+    const long long Bc = p.Bc = each_chunk(VS_WS_TARGET, per_image, B);
     const long long slots = sets * Bc;
     p.spec = 0;
     p.ab = p.spec + slots * 24 * VS_NN;
@@ -425,8 +405,6 @@ VsPlan vsi_plan(int na, int B, int H, int W, int k) {
     p.ok = true;
     return p;
 }
-
-bool vs_finite(double v) { return v == v && v - v == 0.0; }
 
 }  // namespace
 
@@ -441,25 +419,13 @@ extern "C" int mtd_vsi_each(const void* const* srcs, int na, const void* target,
     const VsPlan p = vsi_plan(na, B, H, W, k);
     if (!p.ok) return MTD_EINVAL;
     for (int j = 0; j < MTD_VSI_OPTIONS; ++j)
-        if (!vs_finite(options[j])) return MTD_EINVAL;
+        if (!each_finite(options[j])) return MTD_EINVAL;
     const VsOpts o = {options[0], options[1], options[2], options[3], options[4], options[5], options[6]};
     if (!(o.c1 > 0.0) || !(o.c2 > 0.0) || !(o.c3 > 0.0) || o.sigma_d == 0.0 || o.sigma_c == 0.0) return MTD_EINVAL;
-    VsImgs imgs = {};
-    VsMap map = {};
-    int sets = 0;
-    imgs.p[sets] = (const float*)target;
-    map.tgt = sets++;
-    for (int a = 0; a < na; ++a) {
-        if (!srcs[a]) return MTD_EINVAL;
-        int at = -1;
-        for (int d = 0; d < sets; ++d)
-            if (imgs.p[d] == (const float*)srcs[a]) at = d;
-        if (at < 0) {
-            imgs.p[sets] = (const float*)srcs[a];
-            at = sets++;
-        }
-        map.src[a] = at;
-    }
+    EachSets imgs;
+    EachMap map;
+    const int sets = each_sets(srcs, na, target, imgs, map);
+    if (sets < 0) return MTD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)ws;
     float2* spec = (float2*)(base + p.spec);

@@ -189,6 +189,26 @@ def _device_cached(cache, key, device, build):
     return got
 
 
+def _parts(on, *shape, device, fill=torch.empty):
+    """The float64 parts tensor of a *_each call, or None when the caller did not ask for parts."""
+    return fill(shape, dtype=torch.float64, device=device) if on else None
+
+
+def _each_call(each, ws_bytes, srcs, out_shape, ws_args, args, rows=None, target=True):
+    """What every *_each function ends in: each(the three source pointers, 3, [the target's,] *args, the float64 result of
+    `out_shape`, [`rows` or NULL -- rows=False: the entry has no parts argument --,] the workspace of ws_bytes(*ws_args), the
+    stream), checked -> the result, or (result, rows) where rows is a tensor."""
+    import ctypes
+    dev = srcs[1].device
+    out = torch.empty(out_shape, dtype=torch.float64, device=dev)
+    ws = K.workspace(ws_bytes(*ws_args), dev)
+    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    head = (ptrs, 3, srcs[1].data_ptr()) if target else (ptrs, 3)
+    tail = () if rows is False else (None if rows is None else rows.data_ptr(),)
+    _lib.check(each(*head, *args, out.data_ptr(), *tail, ws.data_ptr(), K.stream_ptr()), each.__name__)
+    return (out, rows) if torch.is_tensor(rows) else out
+
+
 def pixel_metrics_each(input, target, pred, clip_pred=False):
     """The sums of pixel_metrics image by image, without a host read: a (3, B, 2) float64 device tensor, [k][i] = (sum of squared
     error, sum of the SSIM map) of slice i of (input, target, pred)[k] against slice i of target -- the bits of a one-slice
@@ -197,15 +217,10 @@ def pixel_metrics_each(input, target, pred, clip_pred=False):
     B, H, W = _image_shape("pixel metrics expect", input, target, pred)
     _need_cuda("pixel metrics", input, target, pred)
     import ctypes
-    srcs = _fp32_sources(input, target, pred)
-    L = _lib.lib()
-    out = torch.empty((3, B, 2), dtype=torch.float64, device=srcs[1].device)
-    ws = K.workspace(L.mtd_image_metrics_each_ws_bytes(3, B, H, W), out.device)
-    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
     clips = (ctypes.c_int * 3)(0, 0, 1 if clip_pred else 0)
-    _lib.check(L.mtd_image_metrics_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, clips, out.data_ptr(), ws.data_ptr(), K.stream_ptr()),
-               "mtd_image_metrics_each")
-    return out
+    L = _lib.lib()
+    return _each_call(L.mtd_image_metrics_each, L.mtd_image_metrics_each_ws_bytes, _fp32_sources(input, target, pred), (3, B, 2),
+                      (3, B, H, W), (B, H, W, clips), rows=False)
 
 
 def _slice_triples(sums, n):
@@ -256,18 +271,11 @@ def iqa_metrics_each(input, target, pred, which=IQA_METRICS, sigma_n_sq=2.0, par
             raise ValueError(f"iqa metrics: {n} needs images of at least {IQA_MIN_SIDE[n]}x{IQA_MIN_SIDE[n]}, got {H}x{W}")
     if not sigma_n_sq > 0:
         raise ValueError(f"iqa metrics: sigma_n_sq must be positive, got {sigma_n_sq!r}")
-    import ctypes
-    srcs = _fp32_sources(input, target, pred)
     mask = sum(1 << IQA_METRICS.index(n) for n in which)
     L = _lib.lib()
-    dev = srcs[1].device
-    out = torch.empty((len(which), 3, B), dtype=torch.float64, device=dev)
-    stage = torch.zeros((3, B, IQA_PARTS), dtype=torch.float64, device=dev) if parts else None
-    ws = K.workspace(L.mtd_iqa_ws_bytes(mask, 3, B, H, W), dev)
-    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
-    _lib.check(L.mtd_iqa_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, mask, float(sigma_n_sq), out.data_ptr(),
-                              stage.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_iqa_each")
-    return (out, stage) if parts else out
+    srcs = _fp32_sources(input, target, pred)
+    return _each_call(L.mtd_iqa_each, L.mtd_iqa_ws_bytes, srcs, (len(which), 3, B), (mask, 3, B, H, W), (B, H, W, mask, float(sigma_n_sq)),
+                      _parts(parts, 3, B, IQA_PARTS, device=srcs[1].device, fill=torch.zeros))
 
 
 def _iqa_triples(which, vals):
@@ -324,18 +332,11 @@ def haarpsi_each(input, target, pred, c=30.0, alpha=4.2, subsample=True, parts=F
     if H < HAARPSI_MIN_SIDE or W < HAARPSI_MIN_SIDE:
         raise ValueError(f"haarpsi needs images of at least {HAARPSI_MIN_SIDE}x{HAARPSI_MIN_SIDE}, got {H}x{W}")
     haarpsi_check_options(c, alpha, subsample)
-    import ctypes
-    srcs = _fp32_sources(input, target, pred)
     sub = 1 if subsample else 0
     L = _lib.lib()
-    dev = srcs[1].device
-    out = torch.empty((3, B), dtype=torch.float64, device=dev)
-    sums = torch.empty((3, B, 4), dtype=torch.float64, device=dev) if parts else None
-    ws = K.workspace(L.mtd_haarpsi_ws_bytes(3, B, H, W, sub), dev)
-    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
-    _lib.check(L.mtd_haarpsi_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, sub, float(c), float(alpha), out.data_ptr(),
-                                  sums.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_haarpsi_each")
-    return (out, sums) if parts else out
+    srcs = _fp32_sources(input, target, pred)
+    return _each_call(L.mtd_haarpsi_each, L.mtd_haarpsi_ws_bytes, srcs, (3, B), (3, B, H, W, sub), (B, H, W, sub, float(c), float(alpha)),
+                      _parts(parts, 3, B, 4, device=srcs[1].device))
 
 
 def haarpsi_per_slice(input, target, pred, c=30.0, alpha=4.2, subsample=True):
@@ -444,18 +445,12 @@ def fsim_each(input, target, pred, scales=4, orientations=4, min_length=6, mult=
         raise ValueError(f"fsim: {H}x{W} images pool (kernel {ks}) to {h}x{w}; the kernels take pooled sides that are powers of two in "
                          f"{FSIM_MIN_SIDE}..{FSIM_MAX_SIDE}")
     _need_cuda("fsim", input, target, pred)
-    import ctypes
     srcs = _fp32_sources(input, target, pred)                    # (the same tensor twice stays the same pointer: transformed once)
+    table, consts = _fsim_tables(h, w, scales, orientations, min_length, mult, sigma_f, delta_theta, srcs[1].device)
     L = _lib.lib()
-    dev = srcs[1].device
-    table, consts = _fsim_tables(h, w, scales, orientations, min_length, mult, sigma_f, delta_theta, dev)
-    out = torch.empty((3, B), dtype=torch.float64, device=dev)
-    rows = torch.empty((3, B, FSIM_SUMS + orientations), dtype=torch.float64, device=dev) if parts else None
-    ws = K.workspace(L.mtd_fsim_ws_bytes(3, B, h, w, scales, orientations), dev)
-    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
-    _lib.check(L.mtd_fsim_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, ks, scales, orientations, float(k), table.data_ptr(), consts.data_ptr(),
-                               out.data_ptr(), rows.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_fsim_each")
-    return (out, rows) if parts else out
+    return _each_call(L.mtd_fsim_each, L.mtd_fsim_ws_bytes, srcs, (3, B), (3, B, h, w, scales, orientations),
+                      (B, H, W, ks, scales, orientations, float(k), table.data_ptr(), consts.data_ptr()),
+                      _parts(parts, 3, B, FSIM_SUMS + orientations, device=srcs[1].device))
 
 
 def fsim_per_slice(input, target, pred, **kw):
@@ -548,18 +543,12 @@ def vsi_each(input, target, pred, c1=1.27, c2=386., c3=130., alpha=0.4, beta=0.0
     import ctypes
     vsi_check_options(c1, c2, c3, alpha, beta, omega_0, sigma_f, sigma_d, sigma_c)
     srcs, B, H, W = _each_sources("vsi", input, target, pred, VSI_MIN_SIDE, VSI_MAX_SIDE)
-    L = _lib.lib()
-    dev = srcs[1].device
     k = vsi_kernel_size(H, W)
-    table = _vsi_table(float(omega_0), float(sigma_f), dev)
-    out = torch.empty((3, B), dtype=torch.float64, device=dev)
-    rows = torch.empty((3, B, VSI_PARTS), dtype=torch.float64, device=dev) if parts else None
-    ws = K.workspace(L.mtd_vsi_ws_bytes(3, B, H, W, k), dev)
-    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
+    table = _vsi_table(float(omega_0), float(sigma_f), srcs[1].device)
     opts = (ctypes.c_double * 7)(c1, c2, c3, alpha, beta, sigma_d, sigma_c)
-    _lib.check(L.mtd_vsi_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, k, table.data_ptr(), opts, out.data_ptr(),
-                              rows.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_vsi_each")
-    return (out, rows) if parts else out
+    L = _lib.lib()
+    return _each_call(L.mtd_vsi_each, L.mtd_vsi_ws_bytes, srcs, (3, B), (3, B, H, W, k), (B, H, W, k, table.data_ptr(), opts),
+                      _parts(parts, 3, B, VSI_PARTS, device=srcs[1].device))
 
 
 def mdsi_each(input, target, pred, c1=140., c2=55., c3=550., combination="sum", alpha=0.6, beta=0.1, gamma=0.2, rho=1., q=0.25, o=0.25,
@@ -572,17 +561,11 @@ def mdsi_each(input, target, pred, c1=140., c2=55., c3=550., combination="sum", 
     import ctypes
     mdsi_check_options(c1, c2, c3, combination, alpha, beta, gamma, rho, q, o)
     srcs, B, H, W = _each_sources("mdsi", input, target, pred, MDSI_MIN_SIDE, MDSI_MAX_SIDE)
-    L = _lib.lib()
-    dev = srcs[1].device
     k = vsi_kernel_size(H, W)
-    out = torch.empty((3, B), dtype=torch.float64, device=dev)
-    rows = torch.empty((3, B, MDSI_PARTS), dtype=torch.float64, device=dev) if parts else None
-    ws = K.workspace(L.mtd_mdsi_ws_bytes(3, B, H, W, k), dev)
-    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
     opts = (ctypes.c_double * 9)(c1, c2, c3, alpha, beta, gamma, rho, q, o)
-    _lib.check(L.mtd_mdsi_each(ptrs, 3, srcs[1].data_ptr(), B, H, W, k, opts, MDSI_COMBINATIONS.index(combination), out.data_ptr(),
-                               rows.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_mdsi_each")
-    return (out, rows) if parts else out
+    L = _lib.lib()
+    return _each_call(L.mtd_mdsi_each, L.mtd_mdsi_ws_bytes, srcs, (3, B), (3, B, H, W, k), (B, H, W, k, opts, MDSI_COMBINATIONS.index(combination)),
+                      _parts(parts, 3, B, MDSI_PARTS, device=srcs[1].device))
 
 
 def vsi_per_slice(input, target, pred, **kw):
@@ -699,23 +682,18 @@ def brisque_each(input, target, pred, *, weights, kernel_size=7, kernel_sigma=7 
     would make a slice depend on its batch), a product map without a negative or a positive value, a zero left or right sigma --
     the slice's score and parts are NaN and the other slices are untouched.  Sides in 16..1024, kernel_size odd in 3..15,
     interpolation 'nearest'; anything else is a ValueError."""
-    import ctypes
     brisque_check_options(kernel_size, kernel_sigma, interpolation)
     table = brisque_weights(weights)
     srcs, B, H, W = _each_sources("brisque", input, target, pred, BRISQUE_MIN_SIDE, BRISQUE_MAX_SIDE)
-    L = _lib.lib()
     dev = srcs[1].device
     table = table.to(dev)
     taps = _device_cached(_brisque_device_tables, ("taps", kernel_size, float(kernel_sigma)), dev,
                           lambda: brisque_gaussian_table(kernel_size, kernel_sigma).to(dev))
     ggd = _device_cached(_brisque_device_tables, ("ggd",), dev, lambda: brisque_ggd_tables().to(dev))
-    out = torch.empty((3, B), dtype=torch.float64, device=dev)
-    rows = torch.empty((3, B, BRISQUE_PARTS), dtype=torch.float64, device=dev) if parts else None
-    ws = K.workspace(L.mtd_brisque_ws_bytes(3, B, H, W), dev)
-    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
-    _lib.check(L.mtd_brisque_each(ptrs, 3, B, H, W, kernel_size, taps.data_ptr(), ggd.data_ptr(), ggd.shape[1], table.data_ptr(), table.shape[0],
-                                  out.data_ptr(), rows.data_ptr() if parts else None, ws.data_ptr(), K.stream_ptr()), "mtd_brisque_each")
-    return (out, rows) if parts else out
+    L = _lib.lib()
+    return _each_call(L.mtd_brisque_each, L.mtd_brisque_ws_bytes, srcs, (3, B), (3, B, H, W),
+                      (B, H, W, kernel_size, taps.data_ptr(), ggd.data_ptr(), ggd.shape[1], table.data_ptr(), table.shape[0]),
+                      _parts(parts, 3, B, BRISQUE_PARTS, device=dev), target=False)
 
 
 def tv_each(input, target, pred, norm_type="l2"):
@@ -723,16 +701,10 @@ def tv_each(input, target, pred, norm_type="l2"):
     read: a (3, B) float64 device tensor.  norm_type 'l1': the sum of |dy| and |dx| of neighbouring pixels; 'l2': the square root of
     the sum of their squares; 'l2_squared': that sum.  All double in a fixed order (mtd_tv_each): a slice's value depends neither
     on the batch it is in nor on the other two image sets; a constant slice gives exactly 0.  Sides in 16..1024 (ValueError)."""
-    import ctypes
     tv_check_options(norm_type)
     srcs, B, H, W = _each_sources("tv", input, target, pred, TV_MIN_SIDE, TV_MAX_SIDE)
     L = _lib.lib()
-    dev = srcs[1].device
-    out = torch.empty((3, B), dtype=torch.float64, device=dev)
-    ws = K.workspace(L.mtd_tv_ws_bytes(3, B, H, W), dev)
-    ptrs = (ctypes.c_void_p * 3)(*(t.data_ptr() for t in srcs))
-    _lib.check(L.mtd_tv_each(ptrs, 3, B, H, W, TV_NORMS.index(norm_type), out.data_ptr(), ws.data_ptr(), K.stream_ptr()), "mtd_tv_each")
-    return out
+    return _each_call(L.mtd_tv_each, L.mtd_tv_ws_bytes, srcs, (3, B), (3, B, H, W), (B, H, W, TV_NORMS.index(norm_type)), rows=False, target=False)
 
 
 def brisque_per_slice(input, target, pred, **kw):
